@@ -7,12 +7,18 @@ With N GPUs the frame's tiles are sharded round-robin over the ranks (one proces
 per-rank RGBW buffers are merged with one RCCL sum-reduce to rank 0 inside the timed region
 (strong scaling of one frame, the reference's distributed mode: exec/distrib/master.rs:91-93).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (HBM-bound
 accounting of SURVEY 8d: 368 B per path vertex + 16 B per pixel) and `cpu_baseline` (the C++
 oracle in faithful-transform mode on all host cores, bounded tile sample, N=1 only).
+
+--dump-outputs DIR writes the RGBW film(s) the last timed step produced as DIR/*.npy (float32), so that two builds can be
+compared output for output: the inputs (seeded scenes, seed 1) are the same from run to run with the same arguments. The film
+is accumulated with float atomics, so two runs of one build agree to rounding (relative ~1e-6), not bit for bit. Rank 0 writes
+the dump of every rank, within one 64 MB budget. In a frame sequence each frame is copied to the host as it finishes (the
+device is idle then); that copy's time is left out of the step's time.
 """
 import argparse
 import json
@@ -29,6 +35,56 @@ HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s HBM3E
 BYTES_PER_VERTEX = 368.0   # SURVEY 8(d) wavefront accounting
 BYTES_PER_PIXEL = 16.0
 WORKLOAD_CONFIG = {"cornell_box": 1, "smallpt": 2, "dragon": 3, "tr15_like": 4}
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs stays under 64 MB in all (headers and the sample index included)
+DUMP_SAMPLE_SEED = 20240607      # fixed: the pixels sampled from a larger output are the same in every run
+
+
+def dump_index(n_films):
+    """The pixels every film of a dump of n_films films keeps: None (whole films) when they fit the budget, otherwise one seeded
+    sample of pixel indices (y * WIDTH + x, sorted), the same for every film. It depends on n_films alone, so every rank of a
+    run computes the same index."""
+    import numpy as np
+    n_pix = WIDTH * HEIGHT
+    if n_films * n_pix * 16 <= DUMP_BUDGET_BYTES:
+        return None
+    k = min(n_pix, (DUMP_BUDGET_BYTES - 4096 * (n_films + 1)) // (n_films * 16 + 8))
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_pix, size=k, replace=False))
+
+
+def reduce_film(film, idx):
+    """One film (a host array of HEIGHT x WIDTH x 4 floats) as it goes into the dump: whole, or the pixels of idx (pixels x 4)."""
+    import numpy as np
+    f = np.asarray(film, dtype=np.float32)
+    return f.reshape(HEIGHT, WIDTH, 4) if idx is None else np.ascontiguousarray(f.reshape(-1, 4)[idx])
+
+
+def write_dump(directory, films, idx):
+    """films: [(name, reduce_film(film, idx))] -- every film of the dump, from every rank; idx: dump_index(len(films)). Writes
+    <name>.npy (whole films), or <name>_sample.npy with the sampled pixel indices in sample_pixel_index.npy (float64, exact).
+    The only writer of a run. Returns the names written."""
+    import numpy as np
+    assert all(f.shape == ((HEIGHT, WIDTH, 4) if idx is None else (len(idx), 4)) for _, f in films)
+    os.makedirs(directory, exist_ok=True)
+    written = []
+    if idx is not None:
+        np.save(os.path.join(directory, "sample_pixel_index.npy"), idx.astype(np.float64))
+        written.append("sample_pixel_index")
+    for name, f in films:
+        name = name if idx is None else name + "_sample"
+        np.save(os.path.join(directory, name + ".npy"), f.astype(np.float32, copy=False))
+        written.append(name)
+    return written
+
+
+def merge_shares(shares):
+    """The films of every rank's share of a frame sequence ([[(name, film)] per rank], names film_frame<N>) in frame order."""
+    return sorted((f for share in shares for f in share), key=lambda f: int(f[0][len("film_frame"):]))
+
+
+def dump_outputs(directory, films):
+    """films: [(name, HEIGHT x WIDTH x 4 float32 array)] of one process -- what the last timed step computed."""
+    idx = dump_index(len(films))
+    return write_dump(directory, [(name, reduce_film(f, idx)) for name, f in films], idx)
 
 
 def cpu_baseline(flat, spp, target_seconds=8.0):
@@ -132,8 +188,10 @@ def pmc_views(workload, samples, kernel_seconds):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps of the reported workload (>= 1)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them (>= 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the film(s) of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--spp", type=int, default=0, help="debug only: the reported config is 1024 spp")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="only the reported line (configs[1]), without the configs[2..4] lines attached to it")
@@ -147,6 +205,8 @@ def main():
                     "frame to frame with tray_scene_update_frame (Scene::update_frame, scene.rs:152-176) inside the timed region; with N GPUs the frames are "
                     "dealt round-robin over the ranks (multi.shard_frames, BASELINE.json configs[4]), each rank renders whole frames, no collective")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -183,9 +243,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_workload(name, want_spp, steps, warmup, warmup_spp=None, frames=1):
+    def run_workload(name, want_spp, steps, warmup, warmup_spp=None, frames=1, keep_outputs=False):
         """K timed steps of one workload (a step = one frame, or a sequence of `frames` frames of the moving workload), bracketed as the
-        contract says; returns the measurements of this rank (and the scene)"""
+        contract says; returns the measurements of this rank (and the scene). keep_outputs: also return the films the last timed step
+        computed, reduced for the dump (m["outputs"], [(name, reduce_film(...))] -- on rank 0 those of every rank -- and m["dump_index"])"""
         tmp = tempfile.mkdtemp(prefix=f"traybench{rank}_")
         frame = args.frame if name == "tr15_like" else 0
         if name == "dragon":
@@ -205,6 +266,10 @@ def main():
                     film.zero_()
                     hip.render_device(scene, fr, (0, 0), step_spp, film.data_ptr(), stream=stream)
                     seq_counts.append(hip.timing(scene))   # (synchronises: the next frame's update waits for the device anyway)
+                    if keep_frames is not None:   # (--dump-outputs, last timed step only: to the host now, the next frame zeroes the film)
+                        t_keep = time.perf_counter()
+                        keep_frames.append((f"film_frame{fr}", reduce_film(film.cpu().numpy(), dump_idx)))
+                        keep_s[-1] += time.perf_counter() - t_keep
                 return
             film.zero_()
             if distributed:
@@ -215,13 +280,18 @@ def main():
                 hip.render_device(scene, frame, (0, 0), step_spp, film.data_ptr(), stream=stream)
 
         seq_counts = []
+        keep_frames = None
+        keep_s = [0.0]   # seconds of the last step spent copying frames for the dump: not part of the step
+        dump_idx = dump_index(frames if seq else 1) if keep_outputs else None
         for _ in range(warmup):
             step(warmup_spp or spp)
         fence()
         kernel_ms, samples, vertices, launches = [], 0, 0, 0
         t0 = time.perf_counter()
         step_ms = []   # wall time of every step (tray_last_timing below waits for the step's launches, so each figure is a finished step)
-        for _ in range(steps):
+        for i in range(steps):
+            if seq and keep_outputs and i == steps - 1:
+                keep_frames = []
             t_step = time.perf_counter()
             seq_counts.clear()
             step(spp)
@@ -233,9 +303,21 @@ def main():
                 tim = hip.timing(scene)   # HIP events on the launch stream around the schedule's kernels
                 kernel_ms.append(tim.render_ms)
                 samples, vertices, launches = tim.samples, tim.vertices, tim.launches
-            step_ms.append((time.perf_counter() - t_step) * 1e3)
+            step_ms.append((time.perf_counter() - t_step - keep_s[-1]) * 1e3)
         fence()
-        elapsed = time.perf_counter() - t0
+        elapsed = time.perf_counter() - t0 - keep_s[-1]
+        outputs = None
+        if keep_outputs:   # the film(s) a caller of this step receives: rank 0's merged frame, or each frame of the sequence
+            if seq:
+                outputs = keep_frames
+                if distributed:   # every rank's share of the sequence to rank 0, the one writer of the dump
+                    shares = [None] * world if rank == 0 else None
+                    dist.gather_object(keep_frames, shares, dst=0)
+                    outputs = merge_shares(shares) if rank == 0 else []
+            elif rank == 0:
+                outputs = [("film", reduce_film(film.cpu().numpy(), dump_idx))]
+            else:
+                outputs = []
         if distributed:
             tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -250,7 +332,7 @@ def main():
         except Exception:
             sched = None
         return {"name": name, "scene": scene, "frame": frame, "spp": spp, "steps": steps, "elapsed": elapsed, "kernel_ms": sum(kernel_ms) / len(kernel_ms), "schedule": sched,
-                "n_frames": frames if seq else 1, "step_ms": step_ms,
+                "n_frames": frames if seq else 1, "step_ms": step_ms, "outputs": outputs, "dump_index": dump_idx,
                 "samples": samples, "vertices": vertices, "launches": launches, "total_samples": total_samples, "total_vertices": total_vertices}
 
     def line_of(m):
@@ -292,7 +374,9 @@ def main():
                   "vertices_per_sample": round(vbar, 4)}
         return value, ms_per_step, config, roofline
 
-    main_m = run_workload(args.workload, args.spp or default_spp[args.workload], args.steps, args.warmup, frames=args.frames)
+    main_m = run_workload(args.workload, args.spp or default_spp[args.workload], args.steps, args.warmup, frames=args.frames,
+                          keep_outputs=args.dump_outputs is not None)
+    dumped = write_dump(args.dump_outputs, main_m["outputs"], main_m["dump_index"]) if args.dump_outputs is not None and rank == 0 else []
     if rank == 0:
         value, ms_per_step, config, roofline = line_of(main_m)
         out = {
@@ -301,6 +385,8 @@ def main():
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic", "config": config, "roofline": roofline,
         }
+        if args.dump_outputs is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "names": dumped}
     # BASELINE.json configs[2..4] beside the reported line (N = 1 only, like the CPU leg): one warm-up launch at a cut-down sample
     # count, then full-size frames -- so that the driver's own run sees every workload, not only cornell_box
     if world == 1 and args.workload == "cornell_box" and not args.spp and not args.no_other_workloads:

@@ -1,8 +1,8 @@
 """The product's loader (csrc/host/scene.cpp -> TrayFlatScene) against an INDEPENDENT reading of the same scene files
 (tests/_indep_loader.py, written from the reference's src/scene.rs alone): oracle and product consume the same TrayFlatScene, so
 without this a loader bug -- a material bound to the wrong object, a transform composed in the wrong order, a plane that is not
-2x2 -- would be invisible to every parity test. Bundled scenes (scenes/*.json, restated from the reference's files) always;
-the reference's own files when /root/reference exists (build container)."""
+2x2 -- would be invisible to every parity test. Bundled scenes (scenes/*.json, restated from the reference's files) and
+the reference's own files (tests/golden/reference_scenes/)."""
 import ctypes as C
 import os
 
@@ -14,7 +14,9 @@ import _indep_loader as I
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = [os.path.join(ROOT, "scenes", n) for n in ("cornell_box.json", "smallpt.json")]
-FILES += [os.path.join("/root/reference/scenes", n) for n in ("cornell_box.json", "smallpt.json") if os.path.exists("/root/reference/scenes")]
+REF_SCENES = os.path.join(ROOT, "tests", "golden", "reference_scenes")
+# (ids relative to the repository: the same on every checkout)
+FILES += [pytest.param(os.path.join(REF_SCENES, n), id="tests/golden/reference_scenes/" + n) for n in ("cornell_box.json", "smallpt.json")]
 
 
 @pytest.mark.parametrize("path", FILES)
@@ -84,9 +86,9 @@ def test_obj_meshes_equal_the_independent_reading(which, tmp_path, built):
         scenes.write_assets(d)
         scene, *_ = T.Scene.load_file(os.path.join(d, "cornell_box.json"))
         obj, model = os.path.join(d, "models", "cube.obj"), "Cube"
-        if os.path.exists("/root/reference/scenes/models/cube.obj"):   # the bundled copy describes the reference's mesh
-            for a, b in zip(I.read_obj_model(obj, model), I.read_obj_model("/root/reference/scenes/models/cube.obj", model)):
-                assert a.shape == b.shape and (a == b).all()
+        # the bundled copy describes the reference's mesh
+        for a, b in zip(I.read_obj_model(obj, model), I.read_obj_model(os.path.join(REF_SCENES, "models", "cube.obj"), model)):
+            assert a.shape == b.shape and (a == b).all()
     else:
         path, ntri = scenes.write_dragon_assets(d, film=(64, 48, 4), grid=48, extent=1.0)
         scene, *_ = T.Scene.load_file(path)

@@ -1,7 +1,7 @@
 """The loader against the reference's own scenes/tr15.json (BASELINE.json configs[4]): 600 frames, a camera and five objects
 / groups on cubic B-splines, ten lights with animated emission, 13 OBJ files with 25 models, 5 MERL BRDFs. The models and
-BRDFs are not distributed with the reference, so seeded stand-ins are generated at the paths the scene names. Runs only
-where /root/reference exists (this container); nothing here travels to the GPU box."""
+BRDFs are not distributed with the reference, so seeded stand-ins are generated at the paths the scene names. The reference's
+scene files are stored under tests/golden/reference_scenes/."""
 import json
 import os
 import shutil
@@ -16,8 +16,7 @@ from tray_rust_amd import _lib as L
 from tray_rust_amd import scenes
 import _oracle as O
 
-TR15 = "/root/reference/scenes/tr15.json"
-pytestmark = pytest.mark.skipif(not os.path.exists(TR15), reason="reference scenes are only present in the build container")
+TR15 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_scenes", "tr15.json")
 
 
 @pytest.fixture(scope="module")
@@ -144,7 +143,7 @@ def test_every_bundled_reference_scene_loads_and_renders(name, tmp_path, built):
 
 def test_generated_cube_and_scenes_equal_the_reference_files(tmp_path, built):
     """scenes.cube_obj() / cornell_box() / smallpt() restate scenes/models/cube.obj, cornell_box.json and smallpt.json (those
-    files do not exist on the GPU box): the flattened scenes must be identical, bit for bit."""
+    files are stored under tests/golden/reference_scenes/): the flattened scenes must be identical, bit for bit."""
     src_dir = os.path.dirname(TR15)
     ref_dir, gen_dir = str(tmp_path / "ref"), str(tmp_path / "gen")
     os.makedirs(os.path.join(ref_dir, "models")); os.makedirs(gen_dir)

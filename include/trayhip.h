@@ -304,9 +304,12 @@ int tray_device_count(int* n);
 int tray_scene_create(const TrayFlatScene* flat, TrayDeviceScene** out);
 /* Scene::update_frame (src/scene.rs:152-176; the frame loop of src/main.rs:91-106 keeps the Scene and rebuilds the instance
  * transforms and BVH<Instance> per frame): `flat` is the SAME scene flattened at another frame. Instances, BVH<Instance>, camera,
- * spline tables, emission keys and the set of moving instances are uploaded anew; meshes, MERL tables, textures, the tile queue,
- * the wavefront pool / queues and the per-path transform cache stay on the device. Waits for the device to be idle. On an error
- * the handle can only be passed to tray_scene_destroy. */
+ * spline tables, emission keys and the set of moving instances are uploaded anew; meshes, MERL tables, textures and the tile queue stay
+ * on the device, and so do the launch buffers -- the wavefront pool / queues, the per-path transform cache and the transform table's buffer --
+ * as far as the new frame can use them: the cache if it has room for the frame's moving instances on the same schedule, the table's buffer
+ * (rebuilt by the frame's first launch that reads it, replaced if it is too small), the pool if the traversal stacks and the kernels are the
+ * same and it is no larger than the per-path cache's lanes or the pool size wished for -- or was sized for launches that read the table.
+ * Waits for the device to be idle. On an error the handle can only be passed to tray_scene_destroy. */
 int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* flat);
 void tray_scene_destroy(TrayDeviceScene* s);
 
@@ -391,9 +394,11 @@ int tray_last_timing(TrayDeviceScene* s, TrayKernelTiming* t);
  * quarters of the pool on streams of their own (0 = rule: 1 from 24 M slots, else 2); slices: work items a tile's samples are cut into
  * (0 = rule; a power of two <= 16). A host that keeps several device scenes on one GPU sets pool_slots so that they fit beside each other
  * (0.47 KB per slot + 112 B per slot and instance that moves within a frame). Takes effect at the next render call (the buffers are freed
- * and allocated anew if the pool's size changes); for a moving scene the pool cannot grow beyond the transform cache allocated at
- * tray_scene_create / tray_scene_update_frame, which follow the setting. If the allocation fails the library halves the pool down to
- * 16 384 slots before it returns TRAY_E_NOMEM, and the handle stays usable. The environment switches TRAYHIP_WF_SLOTS / _PIPES / _SLICES
+ * and allocated anew if the pool's size changes). A launch of a moving scene that evaluates transforms per path (tray_scene_set_transform_table)
+ * reads a per-path cache with a record for every pool slot: its pool is no larger than the cache's budget (the library's rule and
+ * TRAYHIP_XF_CACHE_BYTES; this setting bounds the pool, not the cache), and a larger pool left by a launch that read the transform table gets a
+ * cache allocated anew for all of its slots -- or, if that would take more than two fifths of the free memory, is allocated anew at the cache's
+ * size. If an allocation fails the library halves the pool down to 16 384 slots before it returns TRAY_E_NOMEM, and the handle stays usable. The environment switches TRAYHIP_WF_SLOTS / _PIPES / _SLICES
  * (measurement only) override these. TRAY_E_INVALID for views > 4 or slices not a power of two <= 16. */
 int tray_scene_set_wavefront(TrayDeviceScene* s, uint32_t pool_slots, uint32_t views, uint32_t slices);
 /* The schedule the last render call on this scene ran with (what tools/pmc_workloads.py records beside its counters). */

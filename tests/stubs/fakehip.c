@@ -3,7 +3,10 @@
  * tray_render_frame_multi / tray_multi_update_frame: one host thread and stream per device, the grouped ncclReduce, the restore of the
  * caller's current device -- executes somewhere before the first 8-GPU run. "Devices" are host memory, streams and events are dummy
  * handles, kernel launches are recorded and do nothing (the films stay zero: this checks the plumbing, not pixels). Every call that
- * matters for the plumbing is appended to the log file named by FAKEHIP_LOG. */
+ * matters for the plumbing is appended to the log file named by FAKEHIP_LOG.
+ * tests/test_launch_buffers_stub.py drives a device scene's launch buffers (wavefront pool, transform cache and table) with three more switches:
+ * FAKEHIP_FREE_BYTES (what hipMemGetInfo reports free), FAKEHIP_MALLOC_MAX (hipMalloc refuses anything larger) and FAKEHIP_WF_DONE (a 4-byte
+ * device-to-host copy -- the wavefront schedule's "tiles done" poll -- reads UINT32_MAX, so that a launch of kernels that do nothing ends). */
 #define _GNU_SOURCE
 #include <pthread.h>
 #include <stdint.h>
@@ -33,15 +36,30 @@ int fakehip_current_device(void) { return t_device; }   /* for the RCCL stand-in
 hipError_t hipGetDeviceCount(int* n) { *n = n_devices(); return 0; }
 hipError_t hipSetDevice(int d) { if (d < 0 || d >= n_devices()) return 101; t_device = d; return 0; }
 hipError_t hipGetDevice(int* d) { *d = t_device; return 0; }
-hipError_t hipMalloc(void** p, size_t n) { *p = calloc(n ? n : 1, 1); return *p ? 0 : 2; }
+hipError_t hipMalloc(void** p, size_t n) {
+    const char* e = getenv("FAKEHIP_MALLOC_MAX");
+    if (e && n > strtoull(e, NULL, 10)) { *p = NULL; logf_("malloc_refused bytes=%zu", n); return 2; }
+    *p = calloc(n ? n : 1, 1);
+    return *p ? 0 : 2;
+}
 hipError_t hipFree(void* p) { free(p); return 0; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned flags) { (void)flags; *p = calloc(n ? n : 1, 1); return *p ? 0 : 2; }
 hipError_t hipHostFree(void* p) { free(p); return 0; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, int kind) { (void)kind; memmove(d, s, n); return 0; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int kind, hipStream_t st) { (void)kind; (void)st; memmove(d, s, n); return 0; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int kind, hipStream_t st) {
+    (void)st;
+    if (kind == 2 /* hipMemcpyDeviceToHost */ && n == 4 && getenv("FAKEHIP_WF_DONE")) { *(uint32_t*)d = UINT32_MAX; return 0; }
+    memmove(d, s, n);
+    return 0;
+}
 hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) { (void)st; memset(d, v, n); return 0; }
-hipError_t hipMemGetInfo(size_t* fr, size_t* tot) { *fr = (size_t)1 << 36; *tot = (size_t)1 << 37; return 0; }
+hipError_t hipMemGetInfo(size_t* fr, size_t* tot) {
+    const char* e = getenv("FAKEHIP_FREE_BYTES");
+    *fr = e ? (size_t)strtoull(e, NULL, 10) : (size_t)1 << 36;
+    *tot = (size_t)1 << 37;
+    return 0;
+}
 hipError_t hipStreamCreate(hipStream_t* s) { *s = malloc(16); *(int*)*s = t_device; logf_("stream_create dev=%d stream=%p", t_device, *s); return 0; }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned f) { (void)f; return hipStreamCreate(s); }
 hipError_t hipStreamDestroy(hipStream_t s) { free(s); return 0; }

@@ -38,6 +38,42 @@ static TraySceneIdentity scene_identity(const TrayFlatScene* f) {
     id.filter_hash = h;
     return id;
 }
+// The three large buffers of a device scene's launches -- the wavefront pool with its queues, chunk records, row bins and overflow stacks; the per-path
+// transform cache; the frame's transform table (dev_geom.h: xf_time_index) -- and what they were sized for. lb_drop frees any of them, a frame update
+// moves them to the next frame's scene and lb_fit drops what it cannot use, launch_prepare picks cache or table per launch and sizes the pool.
+struct WfBuffers {   // the wavefront schedule's pool and the buffers that go with it (wf_alloc; 0.47 KB per slot)
+    WfPool pool{nullptr, 0};
+    bool ready = false;                  // every buffer below exists (a failed allocation leaves this false)
+    WfChunk* d_chunks = nullptr;         // n_chunks of them, and as many row bins
+    float* d_bins = nullptr;
+    uint32_t n_chunks = 0;
+    uint32_t *d_wf_counters = nullptr, *h_done = nullptr;   // [0] tile counter, [1] tiles done; pinned host mirror of tiles done
+    uint32_t* d_queues = nullptr;        // ray queues A, B, C (n_slots each) + WF_QCTL_WORDS counters
+    uint32_t* d_kind_queues = nullptr;   // WF_MAT_KINDS x n_slots slot indices
+    uint32_t* d_bin_ctl = nullptr;       // ray binning before the traversal stages (wavefront.h: k_wf_bin_hist): per view and stage, histogram + cursors of every segment
+    uint32_t* d_stack_overflow = nullptr; size_t ovf_entries = 0;   // entries per view of the schedule (WF_PIPES_MAX of them)
+    uint32_t n_blocks_trace = 0;         // persistent grid of k_wf_trace_dyn
+    uint32_t trace_lds_depth = 0, trace_lds_bytes = 0;   // LDS part of the dynamic-fetch kernel's stacks; deeper entries go to d_stack_overflow
+    bool wf_sort = true;                 // material sort of the shading stage (k_wf_begin's LDS counting sort -> k_wf_query_kind); off for textured scenes
+    uint32_t stack_bytes = 0, quad_stack_words = 0;   // the scene's traversal stacks and ...
+    bool animated = false;               // ... kernels the buffers were sized for
+    std::vector<void*> allocs;           // the device buffers above
+};
+struct LaunchBuffers {
+    bool wavefront = false;              // the schedule the cache's layout and the pool were made for
+    WfBuffers wf;
+    bool wf_shrunk = false;              // the pool came out smaller than asked for (allocation failed, halved): frame updates keep it
+    // the per-path transform cache (wavefront: one record of TR_XF_REC floats per pool slot and moving instance; tile kernel: one column per resident thread)
+    float* xf_cache = nullptr; size_t xf_cache_bytes = 0;
+    uint32_t xf_cache_lanes = 0;         // paths the cache has room for; for a wavefront cache that does not exist yet: its budget (lb_fit)
+    float* d_xf_table = nullptr;         // the frame's transform table, built by the first launch that wants it
+    uint32_t xf_table_stride = 0, xf_table_cap = 0;   // records per time index in use / room for (the next frames of a sequence may move more instances)
+    bool xf_table_built = false;         // ... for THIS frame (a frame update hands the buffer on, the frame's first launch that wants the table builds it)
+    hipEvent_t xf_table_ev = nullptr;    // recorded behind k_xf_table_build on xf_table_stream: a launch of the frame on ANOTHER stream waits for it
+    hipStream_t xf_table_stream = nullptr;
+    bool last_used_table = false;        // the last launch read the table
+    bool owns_any() const { return wf.ready || xf_cache || d_xf_table; }
+};
 struct TrayDeviceScene {
     int device = 0;
     DevScene dev{};
@@ -46,7 +82,6 @@ struct TrayDeviceScene {
     std::vector<TrayDevBuf> bufs;        // the named uploads among `allocs`: what tray_scene_update_frame can carry over to the next frame
     TraySceneIdentity identity{};
     TrayDeviceScene* donor = nullptr;    // while a frame update builds the new state: the previous frame's scene, whose buffers may be taken
-    size_t xf_cache_bytes = 0;
     bool broken = false;                 // a frame update failed half way: only tray_scene_destroy is valid
     uint2* d_tiles = nullptr;      // full Morton queue
     uint32_t n_tiles = 0;
@@ -60,54 +95,29 @@ struct TrayDeviceScene {
     uint32_t launches = 0;
     int n_blocks = 0;
     uint32_t n_materials = 0;
-    // wavefront mode (lazily allocated)
-    WfPool pool{nullptr, 0};
-    bool wf_ready = false;               // every buffer below exists (a failed allocation leaves this false for good)
-    WfChunk* d_chunks = nullptr;
-    float* d_bins = nullptr;
-    uint32_t* d_wf_counters = nullptr;   // [0] tile counter, [1] tiles done
-    uint32_t* h_done = nullptr;          // pinned host mirror of tiles done
-    uint32_t n_chunks = 0;
+    LaunchBuffers lb;                    // wavefront pool, per-path transform cache, transform table
     uint32_t stack_bytes = 0;   // dynamic LDS of every kernel that traverses: stack depth x TR_BLOCK x 4
     bool wavefront = false;   // TRAYHIP_MODE=wave selects the stage-kernel schedule (wavefront.h)
     bool animated = false;    // something moves while the shutter is open: the <ANIM = true> kernels run
     uint32_t deferred_n_moving = 0;
     int feat = FEAT_ALL;              // lobe kinds of the scene's materials that need the large kernels (dev_bsdf.h)
-    uint32_t* d_queues = nullptr;     // wavefront schedule: ray queues A, B, C (n_slots each) + WF_QCTL_WORDS counters
-    uint32_t n_blocks_trace = 0;      // persistent grid of k_wf_trace_dyn
     std::vector<TrayMesh> paired_meshes;   // the meshes with node_offset / node_count in device order (what the `meshes` buffer holds)
     std::vector<uint32_t> quad_first;      // per mesh: entry record of its tree in the `mesh_quads` buffer (host/gates.hpp: QuadTrees)
     size_t n_mesh_quads = 0;               // records of the BVH<Triangle>s at the head of the `quads` buffer
     uint32_t quad_mesh_pend = 0;           // most node entries a traversal of one BVH<Triangle>'s quad records can have pending
     uint32_t quad_stack_words = 0;         // stack words per lane the wavefront traversal needs for this frame's trees
-    uint32_t* d_fallback = nullptr;        // slots of the rays k_wf_trace_dyn hands to k_wf_trace_fallback (one word per pool slot)
     bool narrow_trees = true;         // every node's offset fits a descriptor (host/gates.hpp): the wavefront traversal keeps nodes as descriptors
     bool ordered_boxes = true;        // every BVH box has min <= max (host/gates.hpp: QuadTrees::ordered)
-    uint32_t trace_lds_depth = 0, trace_lds_bytes = 0;   // LDS part of the dynamic-fetch kernel's stacks; deeper entries go to d_stack_overflow
-    uint32_t* d_stack_overflow = nullptr;
-    size_t ovf_entries = 0;              // ... per view of the schedule (WF_PIPES_MAX of them)
-    DevScene launch_dev{};               // what the kernels of the current render call get: `dev`, or `dev` with the transform table in the cache's place
+    DevScene launch_dev{};               // what the kernels of the current render call get: `dev` with the transform cache, or the table in its place (launch_prepare)
     bool camera_animated = false;
-    float* d_xf_table = nullptr;         // the frame's transform table (dev_geom.h: xf_time_index), built by the first launch that wants it
-    uint32_t xf_table_stride = 0;
-    uint32_t xf_table_cap = 0;           // records per time index the buffer has room for (>= xf_table_stride: the next frames of a sequence may move more instances)
     uint32_t xf_movable = 0;             // instances (+ camera) whose transform has a level of several keyframes: what ANY frame of the sequence can move
-    bool xf_table_built = false;         // ... for THIS frame (a frame update takes the buffer over and builds anew)
-    hipEvent_t xf_table_ev = nullptr;    // recorded behind k_xf_table_build: a later launch of the frame on ANOTHER stream waits for it
-    hipStream_t xf_table_stream = nullptr;   // the stream the build was put on
     int xf_table_req = -1;               // tray_scene_set_transform_table: -1 = by the launch's sample count, 0 = never, 1 = always
-    bool last_used_table = false;
-    std::vector<void*> wf_allocs;        // the wavefront buffers among `allocs` (tray_scene_set_wavefront frees them to change the pool's size)
     uint32_t wf_req_slots = 0, wf_req_views = 0, wf_req_slices = 0;   // tray_scene_set_wavefront: 0 = the library's own rule
-    bool wf_shrunk = false;              // the pool came out smaller than asked for (allocation failed, halved): frame updates keep it
     uint32_t last_views = 0, last_slices = 0;   // shape of the last wavefront launch (tray_last_schedule)
     bool last_was_wavefront = false;
     hipStream_t wf_streams[WF_PIPES_MAX] = {nullptr, nullptr, nullptr, nullptr};   // streams of views 1.. (view 0 runs on the caller's), created on first use
     hipEvent_t wf_fork = nullptr, wf_join[WF_PIPES_MAX] = {nullptr, nullptr, nullptr, nullptr};
     bool light_filter = false;        // a sphere light or specular lobes: the tile kernel with mis_ray_filter (dev_integrator.h) compiled in
-    bool wf_sort = true;              // material sort of the shading stage (k_wf_begin's LDS counting sort -> k_wf_query_kind); off for textured scenes
-    uint32_t* d_kind_queues = nullptr;   // WF_MAT_KINDS x n_slots slot indices
-    uint32_t* d_bin_ctl = nullptr;       // ray binning before the traversal stages (wavefront.h: k_wf_bin_hist): per view and stage, histogram + cursors of every segment
     WfBinGrid bin_grid{};                // the cells of the frame's BVH<Instance> box
     bool wf_fused = true;                // fused shading between the traversals (wavefront.h: k_wf_shade_kind); TRAYHIP_WF_FUSED=0|1 overrides
     uint32_t wf_bin_stages = 0u;         // bit 0: stage A rays are binned, bit 1: stage B rays (TRAYHIP_WF_BIN overrides)
@@ -130,9 +140,6 @@ static thread_local int g_device = 0;
         }                                                                                                 \
     } while (0)
 
-static void forget_alloc(TrayDeviceScene* s, void* p) {
-    s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), p), s->allocs.end());
-}
 // Device copy of a host array under a name. During a frame update (s->donor set) a buffer of the same name and size is taken from
 // the previous frame's scene instead of allocated: `unchanged` arrays (meshes, MERL tables, textures, the tile queue: the caller
 // passes the same scene at another frame, tray_scene_update_frame) keep their content, the others are overwritten.
@@ -146,7 +153,7 @@ static int upload(TrayDeviceScene* s, const char* key, bool unchanged, const T* 
         for (size_t i = 0; i < don->bufs.size(); ++i)
             if (std::strcmp(don->bufs[i].key, key) == 0 && don->bufs[i].bytes == bytes) {
                 d = don->bufs[i].ptr;
-                forget_alloc(don, d);
+                don->allocs.erase(std::remove(don->allocs.begin(), don->allocs.end(), d), don->allocs.end());
                 don->bufs.erase(don->bufs.begin() + (long)i);
                 reused = true;
                 break;
@@ -195,13 +202,14 @@ struct WfView {
 template <int ANIM>
 static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride, uint32_t spp,
                      uint32_t kf, float* rgbw_dev, uint32_t slice_shift) {
+    const WfBuffers& w = s->lb.wf;
     const dim3 grid(v.n_chunks), block(TR_BLOCK);
     const dim3 qgrid((v.n_chunks + WF_SEGS - 1u) / WF_SEGS * WF_SEGS);   // one-thread-per-entry kernels: block b reads segment b % WF_SEGS
-    const dim3 tgrid(std::min<uint32_t>(s->n_blocks_trace, v.n_chunks));
+    const dim3 tgrid(std::min<uint32_t>(w.n_blocks_trace, v.n_chunks));
     const uint32_t n_active = v.n_chunks * TR_BLOCK;
     hipStream_t stream = v.stream;
     hipLaunchKernelGGL(k_wf_advance<ANIM>, grid, block, 0, stream, v.dev, v.pool, v.chunks, v.bins, tiles, tile_count, chunk, chunk_stride,
-                       spp, kf, rgbw_dev, s->d_wf_counters, s->d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift);
+                       spp, kf, rgbw_dev, w.d_wf_counters, w.d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift);
     hipLaunchKernelGGL(k_wf_regen<ANIM>, qgrid, block, 0, stream, v.dev, v.pool, v.chunks, tiles, chunk, chunk_stride, spp, kf, s->d_stats, v.qr, v.qa, v.qctl, slice_shift);
     // (each traversal is followed by the few-thread kernel that traces the rays it handed over to the reference's binary traversal:
     // direction components that are zero / denormal / not finite -- normally none, the kernel reads one word and exits. The deferred rays'
@@ -217,7 +225,7 @@ static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, ui
         hipLaunchKernelGGL(k_wf_bin_scatter<0>, bgrid, block, 0, stream, v.pool, v.qa, v.qc, v.qctl, v.bin_ctl, s->bin_grid);
         trace_a = v.qc;
     }
-    hipLaunchKernelGGL((k_wf_trace_dyn<0, ANIM>), tgrid, block, s->trace_lds_bytes, stream, v.dev, v.pool, trace_a, v.qctl, s->d_stats, s->trace_lds_depth, v.overflow, v.qb, 0u);
+    hipLaunchKernelGGL((k_wf_trace_dyn<0, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, trace_a, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qb, 0u);
     hipLaunchKernelGGL((k_wf_trace_fallback<0, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qb, 0u);
     // the control words of every queue are cleared HERE, between the traversal of stage A and the first shading kernel: queue A, its cursors, the
     // regeneration queue and stage A's fallback counter are consumed, stage B's and the material kinds' are not produced yet -- and the count of
@@ -232,7 +240,7 @@ static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, ui
         WF_SHADE_KIND(TRAY_MAT_MATTE); WF_SHADE_KIND(TRAY_MAT_PLASTIC); WF_SHADE_KIND(TRAY_MAT_METAL); WF_SHADE_KIND(TRAY_MAT_GLASS);
         WF_SHADE_KIND(TRAY_MAT_ROUGH_GLASS); WF_SHADE_KIND(TRAY_MAT_SPECULAR_METAL); WF_SHADE_KIND(TRAY_MAT_MERL);
 #undef WF_SHADE_KIND
-        hipLaunchKernelGGL((k_wf_trace_dyn<1, ANIM>), tgrid, block, s->trace_lds_bytes, stream, v.dev, v.pool, v.qb, v.qctl, s->d_stats, s->trace_lds_depth, v.overflow, v.qc, 1u);
+        hipLaunchKernelGGL((k_wf_trace_dyn<1, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, v.qb, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qc, 1u);
         hipLaunchKernelGGL((k_wf_trace_fallback<1, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qc, 1u);
         return;
     }
@@ -244,7 +252,7 @@ static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, ui
         hipLaunchKernelGGL(k_wf_bin_scatter<1>, bgrid, block, 0, stream, v.pool, v.qb, v.qa, v.qctl, ctl_b, s->bin_grid);
         trace_b = v.qa;
     }
-    hipLaunchKernelGGL((k_wf_trace_dyn<1, ANIM>), tgrid, block, s->trace_lds_bytes, stream, v.dev, v.pool, trace_b, v.qctl, s->d_stats, s->trace_lds_depth, v.overflow, v.qc, 0u);
+    hipLaunchKernelGGL((k_wf_trace_dyn<1, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, trace_b, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qc, 0u);
     hipLaunchKernelGGL((k_wf_trace_fallback<1, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qc, 0u);
     uint32_t* const qc = WF_FOLD_C ? nullptr : v.qc;   // (WF_FOLD_C: stage C rays travel with the next round's stage A rays, no queue and no launch of their own)
     if (v.kq) {   // kind-pure shading over the sorted queues: one launch per material kind the scene contains
@@ -255,7 +263,7 @@ static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, ui
     } else hipLaunchKernelGGL((k_wf_query<ANIM, FEAT_ALL | FEAT_TEX>), grid, block, 0, stream, v.dev, v.pool, n_active, qc, v.qctl, s->d_stats, v.qa);
     if (WF_FOLD_C) return;
     // (builds without WF_FOLD_C: the deferred rays of stage C go to B's buffer -- A's holds the next round's continuation rays by now)
-    hipLaunchKernelGGL((k_wf_trace_dyn<2, ANIM>), tgrid, block, s->trace_lds_bytes, stream, v.dev, v.pool, v.qc, v.qctl, s->d_stats, s->trace_lds_depth, v.overflow, v.qb, 0u);
+    hipLaunchKernelGGL((k_wf_trace_dyn<2, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, v.qc, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qb, 0u);
     hipLaunchKernelGGL((k_wf_trace_fallback<2, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qb, 0u);
 }
 
@@ -263,51 +271,75 @@ static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, ui
 // moving scenes never more than the per-path transform cache (112 B per slot and instance that moves within the frame) can hold within two
 // fifths of the device's free memory; a few hundred thousand slots already fill the chip, but every stage kernel ends with the tail of its
 // slowest rays and fewer, larger rounds pay it less often
-// reclaimable: bytes a frame update's donor still holds that the new frame either takes over or frees (its pool and transform cache):
-// they count as free, or the budget -- and with it the pool size -- would depend on which frame came first
 // bytes of the schedule's buffers per pool slot (pool fields, three ray queues + regeneration queue, kind queues, fallback word, row bins per chunk)
 static size_t wf_bytes_per_slot() {
     return (size_t)F_COUNT * sizeof(float) + (3 * WF_RAY_WORDS + 1) * sizeof(uint32_t) + WF_MAT_KINDS * sizeof(uint32_t) +
            ((size_t)ROWBIN_SIZE * sizeof(float) + sizeof(WfChunk)) / TR_BLOCK;
 }
-// what the caller (tray_scene_set_wavefront), the environment or the default ask for, before memory is looked at
-static uint32_t wf_slot_wish(const TrayDeviceScene* s) {
+// what `req_slots` (tray_scene_set_wavefront; 0 = none), the environment or the default ask for, before memory is looked at
+static uint32_t wf_slot_wish(const TrayDeviceScene* s, uint32_t req_slots) {
     uint32_t n_slots = WF_SLOTS;
-    if (s->wf_req_slots) n_slots = std::max<uint32_t>(s->wf_req_slots, 64u * TR_BLOCK) / TR_BLOCK * TR_BLOCK;   // tray_scene_set_wavefront
+    if (req_slots) n_slots = std::max<uint32_t>(req_slots, 64u * TR_BLOCK) / TR_BLOCK * TR_BLOCK;   // tray_scene_set_wavefront
     if (const char* e = getenv("TRAYHIP_WF_SLOTS")) n_slots = (uint32_t)std::max(256l, atol(e)) / TR_BLOCK * TR_BLOCK;
     const uint64_t by_tiles = (uint64_t)std::max<uint32_t>(s->n_tiles, 1u) * TR_BLOCK * WF_MAX_SLICES;   // (a tile's samples can be cut into that many work items: launch_wavefront)
     return (uint32_t)std::min<uint64_t>(n_slots, by_tiles);
 }
-// with_cache: the launch evaluates transforms per path (xf_cache_ensure will want 112 B per slot and moving instance); a launch that reads the
-// frame's transform table instead allocates no cache, and its pool is bounded by the pool's own bytes alone
-static uint32_t wf_slot_count(const TrayDeviceScene* s, size_t reclaimable = 0, bool with_cache = true) {
-    uint64_t slots = wf_slot_wish(s);
+static size_t device_free_bytes() {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
+    return free_b;
+}
+// `slots` within the share of the memory the pool may take, cut to the round-6 shape; free_b: what counts as free (hipMemGetInfo + what a frame update reclaims)
+static uint32_t wf_slot_fit(const TrayDeviceScene* s, uint64_t slots, size_t free_b, uint32_t req_slots) {
     // the pool with its queues and bins (~0.47 KB per slot: 15 GB at 32 M) stays within a third of what is free now -- static scenes too
-    // (a host that keeps several device scenes gets pools that fit beside each other; launch_wavefront halves on top if hipMalloc refuses)
+    // (a host that keeps several device scenes gets pools that fit beside each other; launch_prepare halves on top if hipMalloc refuses)
     {
-        const uint64_t fit = (uint64_t)(free_b + reclaimable) / 3u / wf_bytes_per_slot() / TR_BLOCK * TR_BLOCK;
+        const uint64_t fit = (uint64_t)free_b / 3u / wf_bytes_per_slot() / TR_BLOCK * TR_BLOCK;
         slots = std::min<uint64_t>(slots, std::max<uint64_t>(fit, (uint64_t)64 * TR_BLOCK));
-    }
-    if (with_cache && s->animated && s->deferred_n_moving > 0) {
-        uint64_t budget = (free_b + reclaimable) / 5 * 2;   // (two fifths of the free memory: 112 B per slot and instance that moves within the frame -- the C5 stand-in has 2 .. 11 of them, 7 .. 39 GB at 32 M slots)
-        if (const char* e = getenv("TRAYHIP_XF_CACHE_BYTES")) budget = (uint64_t)std::max(0ll, atoll(e));
-        const uint64_t per_slot = (uint64_t)s->deferred_n_moving * TR_XF_REC * sizeof(float);
-        const uint64_t fit = budget / per_slot / TR_BLOCK * TR_BLOCK;
-        slots = std::min<uint64_t>(slots, std::max<uint64_t>(fit, (uint64_t)64 * TR_BLOCK));   // (at least 64 chunks: below that the schedule cannot fill the chip)
     }
     // (round 6) the schedule is fastest with ONE work item per chunk (profiles/r06_c5_pool_128m.txt: 96 M slots under 16 slices per tile lose to 64 M under 8), so a
     // pool that memory cut below the film's 16 slices per tile is cut further to the next tiles x 256 x 2^k below it -- never to less than one chunk per tile
     {
         const uint64_t per_tile_level = (uint64_t)std::max<uint32_t>(s->n_tiles, 1u) * TR_BLOCK;
-        if (slots > per_tile_level && !s->wf_req_slots && !getenv("TRAYHIP_WF_SLOTS")) {
+        if (slots > per_tile_level && !req_slots && !getenv("TRAYHIP_WF_SLOTS")) {
             uint64_t fit = per_tile_level;
             while (fit * 2u <= slots && fit * 2u <= per_tile_level * WF_MAX_SLICES) fit *= 2u;
             slots = fit;
         }
     }
     return (uint32_t)slots;
+}
+// the pool of a launch that reads no per-path cache (a static scene, or the frame's transform table instead: ADVICE round 5) is bounded by its own bytes alone
+static uint32_t wf_slot_count(const TrayDeviceScene* s) { return wf_slot_fit(s, wf_slot_wish(s, s->wf_req_slots), device_free_bytes(), s->wf_req_slots); }
+// The lanes of a moving scene's per-path transform cache (the largest pool a launch that reads it can have): the pool's rule, and the cache within two
+// fifths of the free memory + `reclaimable` (lb_fit). The library's rule and the environment alone: tray_scene_set_wavefront bounds the pool, not the cache.
+static uint32_t xf_cache_budget(const TrayDeviceScene* s, size_t reclaimable) {
+    const size_t free_b = device_free_bytes() + reclaimable;
+    uint64_t budget = free_b / 5 * 2;   // (two fifths of the free memory: the C5 stand-in has 2 .. 11 moving instances, 7 .. 39 GB at 32 M slots)
+    if (const char* e = getenv("TRAYHIP_XF_CACHE_BYTES")) budget = (uint64_t)std::max(0ll, atoll(e));
+    const uint64_t per_slot = (uint64_t)s->deferred_n_moving * TR_XF_REC * sizeof(float);
+    const uint64_t fit = budget / per_slot / TR_BLOCK * TR_BLOCK;
+    const uint64_t slots = std::min<uint64_t>(wf_slot_wish(s, 0u), std::max<uint64_t>(fit, (uint64_t)64 * TR_BLOCK));   // (at least 64 chunks: below that the schedule cannot fill the chip)
+    return wf_slot_fit(s, slots, free_b, 0u);
+}
+
+// frees the parts of the launch buffers `what` names (the caller has made sure that no launch still reads them)
+enum : unsigned { LB_POOL = 1u, LB_CACHE = 2u, LB_TABLE = 4u, LB_ALL = 7u };
+static void lb_drop(LaunchBuffers& b, unsigned what) {
+    if (what & LB_POOL) {
+        for (void* p : b.wf.allocs) (void)hipFree(p);
+        if (b.wf.h_done) (void)hipHostFree(b.wf.h_done);
+        b.wf = WfBuffers{};
+    }
+    if (what & LB_CACHE) {   // (the lanes stay: before a wavefront cache is allocated anew they are its budget)
+        if (b.xf_cache) (void)hipFree(b.xf_cache);
+        b.xf_cache = nullptr; b.xf_cache_bytes = 0;
+    }
+    if (what & LB_TABLE) {
+        if (b.d_xf_table) (void)hipFree(b.d_xf_table);
+        if (b.xf_table_ev) (void)hipEventDestroy(b.xf_table_ev);
+        b.d_xf_table = nullptr; b.xf_table_cap = b.xf_table_stride = 0u; b.xf_table_built = false; b.xf_table_ev = nullptr; b.xf_table_stream = nullptr;
+    }
 }
 
 extern "C" {
@@ -332,14 +364,13 @@ void tray_scene_destroy(TrayDeviceScene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     for (void* p : s->allocs) (void)hipFree(p);
+    lb_drop(s->lb, LB_ALL);
     if (s->d_smp) (void)hipFree(s->d_smp);
-    if (s->h_done) (void)hipHostFree(s->h_done);
     for (int k = 0; k < WF_PIPES_MAX; ++k) {
         if (s->wf_streams[k]) (void)hipStreamDestroy(s->wf_streams[k]);
         if (s->wf_join[k]) (void)hipEventDestroy(s->wf_join[k]);
     }
     if (s->wf_fork) (void)hipEventDestroy(s->wf_fork);
-    if (s->xf_table_ev) (void)hipEventDestroy(s->xf_table_ev);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     delete s;
@@ -358,6 +389,43 @@ static const void* tile_kernel(const TrayDeviceScene* s) {
     return s->animated ? TK_F(1) : TK_F(0);
 #undef TK_F
 #undef TK
+}
+
+// bytes of a per-path transform cache of `lanes` paths (records of the wavefront schedule / rows of columns of the tile kernel: dev_anim.h)
+static size_t xf_cache_bytes_for(const TrayDeviceScene* s, uint32_t lanes) {
+    return (size_t)s->deferred_n_moving * (s->wavefront ? TR_XF_REC : TR_XF_WORDS) * lanes * sizeof(float);
+}
+static int xf_cache_alloc(TrayDeviceScene* s, uint32_t lanes) {
+    const size_t bytes = xf_cache_bytes_for(s, lanes);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("hipMalloc of the per-path transform cache failed: " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(s->deferred_n_moving) +
+                  " moving instances x " + std::to_string(lanes) + " paths (tray_scene_set_wavefront / TRAYHIP_WF_SLOTS / TRAYHIP_XF_CACHE_BYTES bound it)");
+        return TRAY_E_NOMEM;
+    }
+    s->lb.xf_cache = static_cast<float*>(p); s->lb.xf_cache_lanes = lanes; s->lb.xf_cache_bytes = bytes;
+    return TRAY_OK;
+}
+// Fits the launch buffers a frame update handed on (none for a new scene) to the frame of `s`: the cache keeps its lanes if it was made for this schedule
+// (the tile kernel's: for as many resident threads), else they are budgeted anew; the pool stays if it was made for these stacks and kernels and is no
+// larger than the cache's lanes or the wish (a pool that memory made smaller stays), or was sized for table launches and the table came along. A kept pool
+// serves as it is (launch_wavefront re-initialises chunk records and control words, the bins are zero between tiles). Returns whether the pool was kept.
+static bool lb_fit(TrayDeviceScene* s) {
+    LaunchBuffers& b = s->lb;
+    const bool moving = s->animated && s->deferred_n_moving > 0;
+    // (what the previous frame held counts as free, or the budget -- and with it the pool size -- would depend on which frame came first)
+    const size_t reclaimable = b.xf_cache_bytes + (b.wf.pool.data ? (size_t)F_COUNT * b.wf.pool.n_slots * sizeof(float) : 0);
+    const bool keep_lanes = moving && b.xf_cache_lanes != 0u && b.wavefront == s->wavefront && (s->wavefront || b.xf_cache_lanes == (uint32_t)s->n_blocks * TR_BLOCK);
+    const uint32_t lanes = !moving ? 0u : keep_lanes ? b.xf_cache_lanes : s->wavefront ? xf_cache_budget(s, reclaimable) : (uint32_t)s->n_blocks * TR_BLOCK;
+    if (!keep_lanes || b.xf_cache_bytes < xf_cache_bytes_for(s, lanes)) lb_drop(b, LB_CACHE);   // (every path fills its columns before it reads them)
+    b.xf_cache_lanes = lanes;
+    const bool keep_pool = b.wf.ready && s->wavefront && b.wf.stack_bytes == s->stack_bytes && b.wf.quad_stack_words == s->quad_stack_words &&
+                           b.wf.animated == s->animated && (b.wf.pool.n_slots <= (lanes ? lanes : wf_slot_wish(s, s->wf_req_slots)) || (b.last_used_table && b.d_xf_table));
+    if (!keep_pool) { lb_drop(b, LB_POOL); b.wf_shrunk = false; }
+    b.wavefront = s->wavefront;
+    b.xf_table_stride = 0u; b.xf_table_built = false; b.last_used_table = false;   // (the table is built anew by the frame's first launch that wants it)
+    return keep_pool;
 }
 
 static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDeviceScene** out) {
@@ -719,7 +787,7 @@ static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDevic
     if (occ != hipSuccess || per_cu < 1) per_cu = 1;
     s->deferred_n_moving = 0;
     for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].animated) s->deferred_n_moving++;
-    {   // how many records per time index a later frame of this scene can need (xf_table_prepare sizes the table's buffer once)
+    {   // how many records per time index a later frame of this scene can need (xf_table_ensure sizes the table's buffer once)
         auto movable = [&](uint32_t first, uint32_t count) {
             for (uint32_t l = first; l < first + count && l < f->n_xf_levels; ++l) if (f->xf_levels[l].kf_count > 1u) return true;
             return false;
@@ -733,80 +801,30 @@ static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDevic
     if (s->deferred_n_moving > 64) {
         tray_scene_destroy(s); set_error("more than 64 instances move within one frame: the per-path transform cache does not cover that"); return TRAY_E_UNSUPPORTED;
     }
-    if (s->animated && s->deferred_n_moving > 0) {   // per-path transform cache (dev_geom.h)
+    if (s->animated && s->deferred_n_moving > 0) {   // the moving instances of the per-path transform cache (dev_geom.h)
         std::vector<uint32_t> ids(s->deferred_n_moving, 0u);
         for (uint32_t i = 0; i < f->n_instances; ++i)
             if (f->instances[i].animated && f->instances[i].moving_slot < ids.size()) ids[f->instances[i].moving_slot] = i;
         const uint32_t* d_ids = nullptr;
         if (upload(s, "moving_ids", false, ids.data(), ids.size(), &d_ids) != TRAY_OK) { tray_scene_destroy(s); return TRAY_E_NOMEM; }
-        // one column per pool slot / per thread; a frame update keeps the previous frame's pool size (the budget of wf_slot_count is a
-        // share of the memory that was free BEFORE the pool existed)
-        const bool keep_lanes = donor && donor->dev.xf_cache_lanes != 0u && donor->wavefront == s->wavefront && (s->wavefront || donor->n_blocks == s->n_blocks);
-        const size_t reclaimable = donor ? donor->xf_cache_bytes + (donor->pool.data ? (size_t)F_COUNT * donor->pool.n_slots * sizeof(float) : 0) : 0;
-        uint32_t lanes = keep_lanes ? donor->dev.xf_cache_lanes : (s->wavefront ? wf_slot_count(s, reclaimable) : (uint32_t)s->n_blocks * TR_BLOCK);
-        const uint32_t n_moving_for_msg = s->deferred_n_moving;
-        void* cache = nullptr;
-        size_t cache_bytes = (size_t)s->deferred_n_moving * (s->wavefront ? TR_XF_REC : TR_XF_WORDS) * lanes * sizeof(float);   // (records per path / rows of columns: dev_anim.h)
-        // (the wavefront schedule's pool follows the cache: if the budget of wf_slot_count -- a share of what hipMemGetInfo calls free -- cannot be
-        // had in one piece, halve the pool rather than fail; the tile kernel's cache has one column per resident thread and cannot shrink)
-        // Round 5: the wavefront schedule's cache (112 B per pool slot and moving instance: 38.5 GB for the tr15 stand-in's 11 at 33 M slots) is
-        // allocated by the first launch that needs it (xf_cache_ensure): launches of many samples index the frame's transform table instead
-        // (xf_table_prepare) and never touch it. A frame update still takes the previous frame's cache over if there is one.
-        const bool lazy = s->wavefront;
-        if (keep_lanes && donor->dev.xf_cache && donor->xf_cache_bytes >= cache_bytes) {   // (every path fills its columns before it reads them)
-            cache = donor->dev.xf_cache;
-            s->xf_cache_bytes = donor->xf_cache_bytes;
-            forget_alloc(donor, cache);
-            donor->dev.xf_cache = nullptr; donor->xf_cache_bytes = 0;
-        } else if (lazy) {
-            s->xf_cache_bytes = 0;
-        } else if (hipMalloc(&cache, cache_bytes) == hipSuccess) {
-            s->xf_cache_bytes = cache_bytes;
-        } else {
-            tray_scene_destroy(s);
-            set_error("hipMalloc of the per-path transform cache failed: " + std::to_string(cache_bytes >> 20) + " MiB for " + std::to_string(n_moving_for_msg) +
-                      " moving instances x " + std::to_string(lanes) + " paths (TRAYHIP_WF_SLOTS / TRAYHIP_XF_CACHE_BYTES bound it)");
-            return TRAY_E_NOMEM;
-        }
-        if (cache) s->allocs.push_back(cache);
-        s->dev.xf_cache = static_cast<float*>(cache);
         s->dev.moving_ids = d_ids;
         s->dev.n_moving = s->deferred_n_moving;
         s->dev.xf_stride = s->deferred_n_moving;
-        s->dev.xf_cache_lanes = lanes;
         s->dev.xf_aos = s->wavefront ? 1u : 0u;
     }
     s->wf_req_slots = donor ? donor->wf_req_slots : 0u; s->wf_req_views = donor ? donor->wf_req_views : 0u; s->wf_req_slices = donor ? donor->wf_req_slices : 0u;
     s->xf_table_req = donor ? donor->xf_table_req : -1;
-    if (donor && donor->d_xf_table) {
-        // the previous frame's transform table serves as the buffer of this frame's, built anew by the first launch (xf_table_prepare checks that this
-        // frame's records fit: freeing and allocating 20 GB costs 4 s -- profiles/r06_d_frame_overheads.txt --, so the buffer is sized once for a sequence)
-        forget_alloc(donor, donor->d_xf_table); s->allocs.push_back(donor->d_xf_table);
-        s->d_xf_table = donor->d_xf_table; s->xf_table_cap = donor->xf_table_cap; s->xf_table_stride = 0u; s->xf_table_built = false;
-        donor->d_xf_table = nullptr; donor->xf_table_cap = 0u;
-    }
-    if (donor && donor->wf_ready && s->wavefront && donor->stack_bytes == s->stack_bytes && donor->quad_stack_words == s->quad_stack_words && donor->animated == s->animated &&
-        (donor->pool.n_slots <= ((s->animated && s->dev.xf_cache_lanes) ? s->dev.xf_cache_lanes : wf_slot_wish(s)) ||   // (a pool that came out smaller than wished -- memory -- stays as it is)
-         (donor->last_used_table && s->d_xf_table))) {   // (a pool sized for launches that read the frame's transform table -- no per-path cache bounds it --: this frame's launches read theirs, xf_table_prepare)
-        // the wavefront schedule's pool, queues, chunk records and row bins (2.2 GB at 8 M slots) serve the next frame as they are:
-        // launch_wavefront re-initialises the chunk records and the control words of every launch, the bins are zero between tiles
-        for (void* p : {(void*)donor->pool.data, (void*)donor->d_chunks, (void*)donor->d_bins, (void*)donor->d_wf_counters, (void*)donor->d_queues,
-                        (void*)donor->d_kind_queues, (void*)donor->d_stack_overflow, (void*)donor->d_fallback, (void*)donor->d_bin_ctl})
-            if (p) { forget_alloc(donor, p); s->allocs.push_back(p); s->wf_allocs.push_back(p); }
-        donor->wf_allocs.clear(); s->wf_shrunk = donor->wf_shrunk;
-        s->pool = donor->pool; s->d_chunks = donor->d_chunks; s->d_bins = donor->d_bins; s->d_wf_counters = donor->d_wf_counters;
-        s->d_queues = donor->d_queues; s->d_kind_queues = donor->d_kind_queues; s->d_stack_overflow = donor->d_stack_overflow; s->d_fallback = donor->d_fallback;
-        s->d_bin_ctl = donor->d_bin_ctl;
-        s->h_done = donor->h_done; donor->h_done = nullptr;
-        s->n_chunks = donor->n_chunks; s->n_blocks_trace = donor->n_blocks_trace; s->trace_lds_depth = donor->trace_lds_depth;
-        s->trace_lds_bytes = donor->trace_lds_bytes; s->wf_sort = donor->wf_sort; s->ovf_entries = donor->ovf_entries;
-        s->wf_ready = true;
-        donor->wf_ready = false; donor->pool.data = nullptr;
-    }
+    // the launch buffers: the previous frame's in one move (freeing and allocating the 20 GB of a table costs 4 s -- profiles/r06_d_frame_overheads.txt --, a
+    // pool seconds more), then lb_fit drops what this frame cannot use
+    if (donor) s->lb = std::exchange(donor->lb, LaunchBuffers{});
+    const uint32_t handed_slots = s->lb.wf.pool.n_slots, handed_table_use = s->lb.last_used_table;   // (TRAYHIP_STATS)
+    const bool pool_kept = lb_fit(s);
     if (donor && getenv("TRAYHIP_STATS"))
         fprintf(stderr, "[trayhip] frame update: pool %s (donor ready %d, wavefront %d, stack %u / %u B, quad stack %u / %u, animated %d / %d, donor slots %u, cache lanes %u, donor used the table %d, table buffer %s)\n",
-                s->wf_ready ? "kept" : "not kept", donor->wf_ready || s->wf_ready ? 1 : 0, s->wavefront ? 1 : 0, donor->stack_bytes, s->stack_bytes, donor->quad_stack_words, s->quad_stack_words,
-                donor->animated ? 1 : 0, s->animated ? 1 : 0, s->pool.n_slots ? s->pool.n_slots : donor->pool.n_slots, s->dev.xf_cache_lanes, donor->last_used_table ? 1 : 0, s->d_xf_table ? "kept" : "none");
+                pool_kept ? "kept" : "not kept", handed_slots ? 1 : 0, s->wavefront ? 1 : 0, donor->stack_bytes, s->stack_bytes, donor->quad_stack_words, s->quad_stack_words,
+                donor->animated ? 1 : 0, s->animated ? 1 : 0, handed_slots, s->lb.xf_cache_lanes, handed_table_use ? 1 : 0, s->lb.d_xf_table ? "kept" : "none");
+    // the tile kernel's cache is allocated here, the wavefront schedule's by the first launch that evaluates per path (launch_prepare)
+    if (s->dev.n_moving && !s->wavefront && !s->lb.xf_cache && xf_cache_alloc(s, s->lb.xf_cache_lanes) != TRAY_OK) { tray_scene_destroy(s); return TRAY_E_NOMEM; }
     s->donor = nullptr;
     *out = s;
     return TRAY_OK;
@@ -836,11 +854,12 @@ int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* f) {
     const int before = g_device;
     g_device = s->device;
     const size_t owned_before = s->allocs.size();
+    const bool had_launch_buffers = s->lb.owns_any();
     const int rc = scene_build(f, s, &n);
     g_device = before;
     if (rc != TRAY_OK) {   // if a buffer has moved to the half-built (and now destroyed) new state the handle can only be destroyed; a refusal before that leaves it as it was
         s->donor = nullptr;
-        if (s->allocs.size() != owned_before) s->broken = true;
+        if (s->allocs.size() != owned_before || (had_launch_buffers && !s->lb.owns_any())) s->broken = true;
         return rc;
     }
     n->sampler_kind = s->sampler_kind; n->smp_min = s->smp_min; n->smp_max = s->smp_max;   // (tray_scene_set_sampler belongs to the handle)
@@ -854,53 +873,47 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
                         uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_);
 
 // every buffer of the wavefront schedule for a pool of n_slots; on failure nothing stays allocated and TRAY_E_NOMEM is returned
-static void wf_free(TrayDeviceScene* s) {
-    for (void* p : s->wf_allocs) { forget_alloc(s, p); (void)hipFree(p); }
-    s->wf_allocs.clear();
-    if (s->h_done) { (void)hipHostFree(s->h_done); s->h_done = nullptr; }
-    s->pool.data = nullptr; s->pool.n_slots = 0; s->d_chunks = nullptr; s->d_bins = nullptr; s->d_wf_counters = nullptr; s->d_queues = nullptr;
-    s->d_kind_queues = nullptr; s->d_stack_overflow = nullptr; s->d_fallback = nullptr; s->d_bin_ctl = nullptr; s->n_chunks = 0; s->wf_ready = false;
-}
 static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
+    WfBuffers& w = s->lb.wf;
     auto grab = [&](size_t bytes, void** out) -> bool {
         void* p = nullptr;
         const hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             set_error("hipMalloc of " + std::to_string(bytes >> 20) + " MiB failed: " + hipGetErrorString(e));
-            wf_free(s);
+            lb_drop(s->lb, LB_POOL);
             return false;
         }
-        s->allocs.push_back(p); s->wf_allocs.push_back(p);
+        w.allocs.push_back(p);
         *out = p;
         return true;
     };
     void* p = nullptr;
-    s->n_chunks = n_slots / TR_BLOCK;
+    w.n_chunks = n_slots / TR_BLOCK;
     if (!grab((size_t)F_COUNT * n_slots * sizeof(float), &p)) return TRAY_E_NOMEM;
-    s->pool.data = static_cast<float*>(p); s->pool.n_slots = n_slots; s->pool.seg_cap = wf_seg_cap(s->n_chunks);
-    const size_t q_cap = (size_t)WF_SEGS * s->pool.seg_cap;   // entries of one queue: WF_SEGS segments (wavefront.h)
-    const uint32_t n_chunks = s->n_chunks;                    // (wf_free resets the scene's fields on a failed grab)
+    w.pool.data = static_cast<float*>(p); w.pool.n_slots = n_slots; w.pool.seg_cap = wf_seg_cap(w.n_chunks);
+    const size_t q_cap = (size_t)WF_SEGS * w.pool.seg_cap;   // entries of one queue: WF_SEGS segments (wavefront.h)
+    const uint32_t n_chunks = w.n_chunks;                    // (lb_drop resets the fields on a failed grab)
     if (!grab((size_t)n_chunks * sizeof(WfChunk), &p)) return TRAY_E_NOMEM;
-    s->d_chunks = static_cast<WfChunk*>(p);
+    w.d_chunks = static_cast<WfChunk*>(p);
     if (!grab((size_t)n_chunks * ROWBIN_SIZE * sizeof(float), &p)) return TRAY_E_NOMEM;
-    s->d_bins = static_cast<float*>(p);
-    if (hipMemset(s->d_bins, 0, (size_t)n_chunks * ROWBIN_SIZE * sizeof(float)) != hipSuccess) { set_error("hipMemset of the row bins failed"); wf_free(s); return TRAY_E_DEVICE; }
+    w.d_bins = static_cast<float*>(p);
+    if (hipMemset(w.d_bins, 0, (size_t)n_chunks * ROWBIN_SIZE * sizeof(float)) != hipSuccess) { set_error("hipMemset of the row bins failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_DEVICE; }
     if (!grab(2 * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    s->d_wf_counters = static_cast<uint32_t*>(p);
+    w.d_wf_counters = static_cast<uint32_t*>(p);
     // ray queues A, B, C, regeneration queue and the control words of their segments, for up to WF_PIPES_MAX views (a view's segments
     // are sized for its own chunks: WF_SEGS * TR_BLOCK entries of rounding per view and queue)
     const size_t q_slack = (size_t)WF_PIPES_MAX * WF_SEGS * TR_BLOCK;
     // (an entry of a ray queue is the ray: WF_RAY_WORDS words; the regeneration queue holds slot indices)
     if (!grab(((3 * WF_RAY_WORDS + 1) * (q_cap + q_slack) + (size_t)WF_PIPES_MAX * WF_QCTL_WORDS) * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    s->d_queues = static_cast<uint32_t*>(p);
+    w.d_queues = static_cast<uint32_t*>(p);
     // ray binning: per view and stage (A, B) the histogram and the cursors of every segment's bins
     if (!grab((size_t)WF_PIPES_MAX * 2u * 2u * WF_SEGS * WF_BINS * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    s->d_bin_ctl = static_cast<uint32_t*>(p);
-    s->wf_sort = !(s->feat & FEAT_TEX);   // the kind-pure kernels read lobes from the material table; textured materials have theirs per hit
-    if (s->wf_sort) {   // shading queues of the material sort (slot indices), one per material kind
+    w.d_bin_ctl = static_cast<uint32_t*>(p);
+    w.wf_sort = !(s->feat & FEAT_TEX);   // the kind-pure kernels read lobes from the material table; textured materials have theirs per hit
+    if (w.wf_sort) {   // shading queues of the material sort (slot indices), one per material kind
         if (!grab((size_t)WF_MAT_KINDS * (q_cap + q_slack) * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-        s->d_kind_queues = static_cast<uint32_t*>(p);
+        w.d_kind_queues = static_cast<uint32_t*>(p);
     }
     {
         int per_cu = 0, cus = 256;
@@ -911,20 +924,21 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
         const uint32_t full_depth = std::max(s->quad_stack_words, 8u);
         uint32_t lds_depth = std::min<uint32_t>(full_depth, (160u * 1024u / WF_TRACE_WAVES) / (TR_BLOCK * (uint32_t)sizeof(uint32_t)));
         if (const char* e = getenv("TRAYHIP_WF_LDS_DEPTH")) lds_depth = std::min<uint32_t>(full_depth, (uint32_t)std::max(1, atoi(e)));
-        s->trace_lds_depth = lds_depth;
-        s->trace_lds_bytes = lds_depth * TR_BLOCK * (uint32_t)sizeof(uint32_t);
-        hipError_t oe = s->animated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 1>, TR_BLOCK, s->trace_lds_bytes)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 0>, TR_BLOCK, s->trace_lds_bytes);
+        w.trace_lds_depth = lds_depth;
+        w.trace_lds_bytes = lds_depth * TR_BLOCK * (uint32_t)sizeof(uint32_t);
+        hipError_t oe = s->animated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 1>, TR_BLOCK, w.trace_lds_bytes)
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 0>, TR_BLOCK, w.trace_lds_bytes);
         if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-        s->n_blocks_trace = (uint32_t)(cus * per_cu);
-        const size_t ovf_entries = (size_t)(full_depth - lds_depth + 1u) * s->n_blocks_trace * TR_BLOCK;   // per view: their traversal kernels overlap
-        s->ovf_entries = ovf_entries;
+        w.n_blocks_trace = (uint32_t)(cus * per_cu);
+        const size_t ovf_entries = (size_t)(full_depth - lds_depth + 1u) * w.n_blocks_trace * TR_BLOCK;   // per view: their traversal kernels overlap
+        w.ovf_entries = ovf_entries;
         if (!grab((size_t)WF_PIPES_MAX * ovf_entries * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-        s->d_stack_overflow = static_cast<uint32_t*>(p);
+        w.d_stack_overflow = static_cast<uint32_t*>(p);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] dynamic-fetch traversal: %u of %u stack entries in LDS, %d workgroups per CU\n", lds_depth, full_depth, per_cu);
     }
-    if (hipHostMalloc(reinterpret_cast<void**>(&s->h_done), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("hipHostMalloc failed"); wf_free(s); return TRAY_E_NOMEM; }
-    s->wf_ready = true;
+    if (hipHostMalloc(reinterpret_cast<void**>(&w.h_done), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("hipHostMalloc failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_NOMEM; }
+    w.stack_bytes = s->stack_bytes; w.quad_stack_words = s->quad_stack_words; w.animated = s->animated;
+    w.ready = true;
     return TRAY_OK;
 }
 
@@ -932,41 +946,20 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
 // The host only polls a "tiles done" word every WF_POLL rounds; kernels of finished chunks exit at once.
 static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                             uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream) {
-    if (!s->narrow_trees) { set_error("wavefront schedule: a BVH of more than 8 388 607 nodes or triangles (the traversal keeps a node as a 32-bit descriptor)"); return TRAY_E_UNSUPPORTED; }
-    if (!s->ordered_boxes) { set_error("wavefront schedule: a BVH box with min > max (or NaN) on some axis; TRAYHIP_MODE=mega renders such a scene with the tile kernel"); return TRAY_E_UNSUPPORTED; }
-    if (!s->wf_ready) {
-        // the pool and its queues: as many slots as wf_slot_count grants; if hipMalloc still refuses (fragmentation, another scene's pool
-        // allocated since), everything allocated so far is freed and half the slots are tried, down to 64 chunks -- then TRAY_E_NOMEM,
-        // with the handle left as it was
-        // (the per-path transform cache was budgeted at creation; a launch that reads the frame's table never allocates it: xf_table_prepare ran before this)
-        uint32_t n_slots = s->last_used_table ? wf_slot_count(s, 0, false)
-                         : (s->animated && s->dev.xf_cache_lanes) ? std::min(s->dev.xf_cache_lanes, wf_slot_wish(s)) : wf_slot_count(s);
-        for (;;) {
-            const int rc = wf_alloc(s, n_slots);
-            if (rc == TRAY_OK) break;
-            if (rc != TRAY_E_NOMEM) return rc;
-            if (n_slots / 2u < 64u * TR_BLOCK) {
-                set_error("the wavefront schedule's buffers could not be allocated even for " + std::to_string(n_slots) + " pool slots (" +
-                          std::to_string((n_slots * wf_bytes_per_slot()) >> 20) + " MiB): " + tray_last_error());
-                return TRAY_E_NOMEM;
-            }
-            n_slots = n_slots / 2u / TR_BLOCK * TR_BLOCK;
-            s->wf_shrunk = true;
-        }
-    }
+    const WfBuffers& w = s->lb.wf;
     // tiles are cut into slices of their samples while the pool has at least as many chunks as the launch then has work items
     // (k_wf_advance; a slice costs its own film resolve: at 8 M slots and 32 400 tiles halving them measured 124 against 132 Msamples/s); a
     // slice keeps at least 16 samples per pixel (TRAYHIP_WF_SLICES overrides: 1, 2, 4)
     uint32_t slice_shift = 0u;
-    while ((1u << (slice_shift + 1u)) <= WF_MAX_SLICES && ((uint64_t)tile_count << (slice_shift + 1u)) <= s->n_chunks && (spp >> (slice_shift + 1u)) >= 16u) ++slice_shift;   // (cut while the items still fit the chunks: one item per chunk is the optimum)
+    while ((1u << (slice_shift + 1u)) <= WF_MAX_SLICES && ((uint64_t)tile_count << (slice_shift + 1u)) <= w.n_chunks && (spp >> (slice_shift + 1u)) >= 16u) ++slice_shift;   // (cut while the items still fit the chunks: one item per chunk is the optimum)
     if (s->wf_req_slices) { slice_shift = 0u; while ((2u << slice_shift) <= s->wf_req_slices && (2u << slice_shift) <= WF_MAX_SLICES && (spp >> (slice_shift + 1u)) >= 1u) ++slice_shift; }   // tray_scene_set_wavefront
     if (const char* e = getenv("TRAYHIP_WF_SLICES")) { slice_shift = 0u; while ((2u << slice_shift) <= (uint32_t)std::max(1, atoi(e)) && (2u << slice_shift) <= WF_MAX_SLICES && (spp >> (slice_shift + 1u)) >= 1u) ++slice_shift; }
     tile_count <<= slice_shift;   // from here on: work items
-    const uint32_t n_chunks = std::min(s->n_chunks, tile_count);
-    HIP_CHECK(hipMemsetAsync(s->d_wf_counters, 0, 2 * sizeof(uint32_t), stream));
+    const uint32_t n_chunks = std::min(w.n_chunks, tile_count);
+    HIP_CHECK(hipMemsetAsync(w.d_wf_counters, 0, 2 * sizeof(uint32_t), stream));
         {   // chunks start in WF_TILE_NEED with done = 0
         std::vector<WfChunk> init(n_chunks, WfChunk{WF_TILE_NEED, 0u});
-        HIP_CHECK(hipMemcpyAsync(s->d_chunks, init.data(), (size_t)n_chunks * sizeof(WfChunk), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(w.d_chunks, init.data(), (size_t)n_chunks * sizeof(WfChunk), hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));   // `init` is pageable host memory
     }
     HIP_CHECK(hipEventRecord(s->ev0, stream));
@@ -981,8 +974,8 @@ static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t ti
     s->last_views = n_views; s->last_slices = 1u << slice_shift; s->last_was_wavefront = true;
     WfView views[WF_PIPES_MAX];
     {
-        const size_t q_total = (size_t)WF_SEGS * s->pool.seg_cap + (size_t)WF_PIPES_MAX * WF_SEGS * TR_BLOCK;   // entries of one queue kind over all views
-        uint32_t* const qbase[4] = {s->d_queues, s->d_queues + WF_RAY_WORDS * q_total, s->d_queues + 2 * WF_RAY_WORDS * q_total, s->d_queues + 3 * WF_RAY_WORDS * q_total};
+        const size_t q_total = (size_t)WF_SEGS * w.pool.seg_cap + (size_t)WF_PIPES_MAX * WF_SEGS * TR_BLOCK;   // entries of one queue kind over all views
+        uint32_t* const qbase[4] = {w.d_queues, w.d_queues + WF_RAY_WORDS * q_total, w.d_queues + 2 * WF_RAY_WORDS * q_total, w.d_queues + 3 * WF_RAY_WORDS * q_total};
         uint32_t* const qctl_base = qbase[3] + q_total;
         size_t q_off = 0;
         uint32_t c0 = 0;
@@ -992,16 +985,16 @@ static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t ti
             v.n_chunks = c1 - c0;
             v.dev = s->launch_dev;
             if (v.dev.xf_cache && !v.dev.xf_table) v.dev.xf_cache += (size_t)c0 * TR_BLOCK * v.dev.n_moving * TR_XF_REC;   // [slot][moving instance][TR_XF_REC] (the table is indexed by time, not by slot)
-            v.pool = s->pool;
+            v.pool = w.pool;
             v.pool.first = c0 * TR_BLOCK;   // (the hit records are slot-major, the other fields field-major: the accessors add the view's first slot)
             v.pool.seg_cap = wf_seg_cap(v.n_chunks);
-            v.chunks = s->d_chunks + c0;
-            v.bins = s->d_bins + (size_t)c0 * ROWBIN_SIZE;
+            v.chunks = w.d_chunks + c0;
+            v.bins = w.d_bins + (size_t)c0 * ROWBIN_SIZE;
             v.qa = qbase[0] + WF_RAY_WORDS * q_off; v.qb = qbase[1] + WF_RAY_WORDS * q_off; v.qc = qbase[2] + WF_RAY_WORDS * q_off; v.qr = qbase[3] + q_off;
             v.qctl = qctl_base + (size_t)k * WF_QCTL_WORDS;
-            v.kq = s->wf_sort ? s->d_kind_queues + (size_t)WF_MAT_KINDS * q_off : nullptr;
-            v.overflow = s->d_stack_overflow + (size_t)k * s->ovf_entries;
-            v.bin_ctl = s->d_bin_ctl ? s->d_bin_ctl + (size_t)k * 2u * 2u * WF_SEGS * WF_BINS : nullptr;
+            v.kq = w.wf_sort ? w.d_kind_queues + (size_t)WF_MAT_KINDS * q_off : nullptr;
+            v.overflow = w.d_stack_overflow + (size_t)k * w.ovf_entries;
+            v.bin_ctl = w.d_bin_ctl ? w.d_bin_ctl + (size_t)k * 2u * 2u * WF_SEGS * WF_BINS : nullptr;
             v.stream = stream;
             if (k > 0) {
                 if (!s->wf_streams[k]) HIP_CHECK(hipStreamCreateWithFlags(&s->wf_streams[k], hipStreamNonBlocking));
@@ -1033,9 +1026,9 @@ static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t ti
         if (round % WF_POLL == WF_POLL - 1) {
             HIP_CHECK(hipGetLastError());
             for (uint32_t k = 1; k < n_views; ++k) HIP_CHECK(hipStreamSynchronize(views[k].stream));
-            HIP_CHECK(hipMemcpyAsync(s->h_done, s->d_wf_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipMemcpyAsync(w.h_done, w.d_wf_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             HIP_CHECK(hipStreamSynchronize(stream));
-            done = *s->h_done >= tile_count;
+            done = *w.h_done >= tile_count;
         }
         if (round > max_rounds) { set_error("wavefront schedule did not terminate"); return TRAY_E_DEVICE; }
     }
@@ -1150,119 +1143,124 @@ static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile
     return TRAY_OK;
 }
 
-// The transform table of a moving scene's frame (dev_geom.h: xf_time_index; k_xf_table_build): wanted when the launch needs every time index
-// about twice over -- from 3e7 camera samples on (a 1080p frame at 16 spp; a GPU's eighth of a 512-spp frame is 1.3e8; building the table costs
-// what 2^24 = 1.7e7 camera samples' evaluations cost, ~1.4 ms per moving instance, but it also takes 1.9 GB per instance) --, or as
-// tray_scene_set_transform_table says. Built once per frame on the launch stream by the first launch that wants it. If the allocation fails
-// the launch evaluates per path. Sets s->launch_dev.
-#ifndef XF_TABLE_MIN_SAMPLES
-#define XF_TABLE_MIN_SAMPLES 30000000ull
-#endif
-// the wavefront schedule's per-path transform cache, on first use (one record of TR_XF_WORDS floats per pool slot and moving instance): as many
-// columns as scene_build budgeted; halved while hipMalloc refuses and the pool does not exist yet, never below the pool's slots once it does
+// The wavefront schedule's per-path cache, with a record for every pool slot: the budgeted lanes or the pool's slots. A pool larger than the budget (sized
+// for table launches) stays if a cache for all of it fits in two fifths of the free memory, else it goes and is sized anew for the cache; a cache too
+// small for the pool is allocated anew. Halved while hipMalloc refuses, never below the pool's slots or 64 chunks.
 static int xf_cache_ensure(TrayDeviceScene* s) {
-    if (!s->wavefront || !s->animated || s->dev.n_moving == 0u || s->dev.xf_cache) return TRAY_OK;
-    // (a pool that was sized for launches reading the frame's table -- no cache bounded it -- can be larger than any cache the device holds: then the
-    // pool goes, the cache takes its budgeted size and launch_wavefront allocates a pool that fits it)
-    if (s->wf_ready && s->dev.xf_cache_lanes && s->pool.n_slots > s->dev.xf_cache_lanes) {
+    LaunchBuffers& b = s->lb;
+    if (!s->wavefront || s->dev.n_moving == 0u) return TRAY_OK;
+    if (b.wf.ready && b.wf.pool.n_slots > b.xf_cache_lanes) {
         size_t free_b = 0, total_b = 0;
-        const size_t need = (size_t)s->dev.n_moving * TR_XF_REC * s->pool.n_slots * sizeof(float);
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-        if (need > free_b / 5u * 2u) { HIP_CHECK(hipDeviceSynchronize()); wf_free(s); }
+        if (xf_cache_bytes_for(s, b.wf.pool.n_slots) > free_b / 5u * 2u) { HIP_CHECK(hipDeviceSynchronize()); lb_drop(b, LB_POOL); }
     }
-    uint32_t lanes = std::max<uint32_t>(s->dev.xf_cache_lanes, s->wf_ready ? s->pool.n_slots : 0u);
-    const uint32_t floor_lanes = s->wf_ready ? s->pool.n_slots : 64u * TR_BLOCK;
-    for (;;) {
-        const size_t bytes = (size_t)s->dev.n_moving * TR_XF_REC * lanes * sizeof(float);
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) == hipSuccess) {
-            s->allocs.push_back(p);
-            s->dev.xf_cache = static_cast<float*>(p); s->dev.xf_cache_lanes = lanes; s->xf_cache_bytes = bytes;
-            return TRAY_OK;
-        }
-        (void)hipGetLastError();
-        if (lanes <= floor_lanes) {
-            set_error("hipMalloc of the per-path transform cache failed: " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(s->dev.n_moving) +
-                      " moving instances x " + std::to_string(lanes) + " paths (tray_scene_set_wavefront / TRAYHIP_XF_CACHE_BYTES bound it)");
-            return TRAY_E_NOMEM;
-        }
-        lanes = std::max(floor_lanes, lanes / 2u / TR_BLOCK * TR_BLOCK);
+    if (b.xf_cache && (!b.wf.ready || b.wf.pool.n_slots <= b.xf_cache_lanes)) return TRAY_OK;
+    if (b.xf_cache) { HIP_CHECK(hipDeviceSynchronize()); lb_drop(b, LB_CACHE); }
+    const uint32_t pool_slots = b.wf.ready ? b.wf.pool.n_slots : 0u, floor_lanes = b.wf.ready ? pool_slots : 64u * TR_BLOCK;
+    for (uint32_t lanes = std::max(b.xf_cache_lanes, pool_slots);; lanes = std::max(floor_lanes, lanes / 2u / TR_BLOCK * TR_BLOCK)) {
+        const int rc = xf_cache_alloc(s, lanes);
+        if (rc == TRAY_OK || lanes <= floor_lanes) return rc;
     }
 }
-static int xf_table_prepare(TrayDeviceScene* s, uint64_t samples, hipStream_t stream) {
-    s->launch_dev = s->dev;
-    s->last_used_table = false;
-    const uint32_t stride = s->dev.n_moving + (s->camera_animated ? 1u : 0u);
-    if (!s->animated || stride == 0u) return TRAY_OK;
-    int want = s->xf_table_req;
-    if (const char* e = getenv("TRAYHIP_XF_TABLE")) want = atoi(e) != 0 ? 1 : 0;
-    // (a table that exists for this frame serves every launch; so does the buffer of the previous frame's: a sequence that rendered through the table goes on
-    // doing so -- its pool may be larger than a per-path cache could cover)
-    if (want < 0) want = (samples >= XF_TABLE_MIN_SAMPLES || s->xf_table_built || s->d_xf_table) ? 1 : 0;
-    if (!want) {
-        const int rc = xf_cache_ensure(s);
-        if (rc == TRAY_OK) { s->launch_dev = s->dev; return TRAY_OK; }
-        if (rc != TRAY_E_NOMEM) return rc;   // (no room for the cache: the table is smaller from a few million slots on)
-    }
-    if (s->d_xf_table && s->xf_table_cap < stride) {   // (the buffer taken over from the previous frame is too small for this frame's records)
-        forget_alloc(s, s->d_xf_table); (void)hipFree(s->d_xf_table); s->d_xf_table = nullptr; s->xf_table_cap = 0u; s->xf_table_built = false;
-    }
-    if (s->d_xf_table && s->xf_table_stride != stride) { s->xf_table_stride = stride; s->xf_table_built = false; }
-    if (!s->d_xf_table) {
+// The transform table of a moving scene's frame (dev_geom.h: xf_time_index; k_xf_table_build) with `stride` records per time index, built once per frame
+// on the launch stream by the first launch that reads it; TRAY_E_NOMEM if the buffer cannot be had
+static int xf_table_ensure(TrayDeviceScene* s, uint32_t stride, hipStream_t stream) {
+    LaunchBuffers& b = s->lb;
+    if (b.d_xf_table && b.xf_table_cap < stride) lb_drop(b, LB_TABLE);   // (the buffer handed on from the previous frame is too small for this frame's records)
+    if (b.d_xf_table && b.xf_table_stride != stride) { b.xf_table_stride = stride; b.xf_table_built = false; }
+    if (!b.d_xf_table) {
         // room for what any frame of the sequence can move (instances whose transforms have several keyframes, tray_scene_create), if that much is to be had
         uint32_t cap = std::max(stride, s->xf_movable);
-        size_t bytes = ((size_t)1 << 24) * cap * TR_XF_REC * sizeof(float);   // 2.1 GB per moving instance
         void* p = nullptr;
         // by the library's own rule (nobody asked for the table) it takes at most a third of what is free: on a device shared with other
-        // allocators 22.5 GB for eleven movers must not be what starves them; then, or if hipMalloc refuses: per-path evaluation
-        bool room = true;
+        // allocators 22.5 GB for eleven movers must not be what starves them
         const bool own_rule = s->xf_table_req < 0 && !getenv("TRAYHIP_XF_TABLE");
         for (;;) {   // (the sequence's headroom first, then this frame's records alone)
-            room = true;
+            const size_t bytes = ((size_t)1 << 24) * cap * TR_XF_REC * sizeof(float);   // 2.1 GB per moving instance
+            bool room = true;
             if (own_rule) {
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) room = bytes <= free_b / 3u; else (void)hipGetLastError();
             }
             if (room && hipMalloc(&p, bytes) == hipSuccess) break;
-            (void)hipGetLastError();
-            p = nullptr;
-            if (cap == stride) break;
-            cap = stride; bytes = ((size_t)1 << 24) * cap * TR_XF_REC * sizeof(float);
+            (void)hipGetLastError(); p = nullptr;
+            if (cap == stride) return TRAY_E_NOMEM;
+            cap = stride;
         }
-        if (!p) {
-            const int rc = xf_cache_ensure(s);
-            s->launch_dev = s->dev;
-            return rc;
-        }
-        s->allocs.push_back(p);
-        s->d_xf_table = static_cast<float*>(p);
-        s->xf_table_stride = stride;
-        s->xf_table_cap = cap;
-        s->xf_table_built = false;
+        b.d_xf_table = static_cast<float*>(p); b.xf_table_stride = stride; b.xf_table_cap = cap; b.xf_table_built = false;
     }
-    if (!s->xf_table_built) {
-        DevScene d = s->dev;   // (the build reads moving_ids, instances, spline tables, camera: none of them depends on the cache fields)
-        const uint32_t n_index = 1u << 24;
-        hipLaunchKernelGGL(k_xf_table_build, dim3(n_index / TR_BLOCK, stride), dim3(TR_BLOCK), 0, stream, d, s->d_xf_table, stride, 0u, n_index);
+    if (!b.xf_table_built) {
+        const uint32_t n_index = 1u << 24;   // (the build reads moving_ids, instances, spline tables, camera of `dev`: none of them is a launch buffer)
+        hipLaunchKernelGGL(k_xf_table_build, dim3(n_index / TR_BLOCK, stride), dim3(TR_BLOCK), 0, stream, s->dev, b.d_xf_table, stride, 0u, n_index);
         HIP_CHECK(hipGetLastError());
         // the build is ordered before this launch by the stream; the frame's later launches may come on other streams (tray_render_tiles_device /
         // tray_render_shard_device take the caller's): they wait for this event instead of reading a table that is still being written
-        if (!s->xf_table_ev) HIP_CHECK(hipEventCreateWithFlags(&s->xf_table_ev, hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(s->xf_table_ev, stream));
-        s->xf_table_stream = stream;
-        s->xf_table_built = true;
-    } else if (stream != s->xf_table_stream && s->xf_table_ev) {
-        HIP_CHECK(hipStreamWaitEvent(stream, s->xf_table_ev, 0));
+        if (!b.xf_table_ev) HIP_CHECK(hipEventCreateWithFlags(&b.xf_table_ev, hipEventDisableTiming));
+        HIP_CHECK(hipEventRecord(b.xf_table_ev, stream));
+        b.xf_table_stream = stream;
+        b.xf_table_built = true;
+    } else if (stream != b.xf_table_stream && b.xf_table_ev) {
+        HIP_CHECK(hipStreamWaitEvent(stream, b.xf_table_ev, 0));
     }
-    s->launch_dev.xf_tab = s->d_xf_table;
-    s->launch_dev.xf_tab_stride = s->xf_table_stride;
-    if (s->wavefront) {   // the stage kernels index the table by the path's time index; the tile kernel keeps its cache columns and fills them from it
-        s->launch_dev.xf_cache = s->d_xf_table;
-        s->launch_dev.xf_table = 1u;
-        s->launch_dev.xf_aos = 1u;
-        s->launch_dev.xf_stride = s->xf_table_stride;
+    return TRAY_OK;
+}
+
+// What a render call's kernels need of the launch buffers: 1. table or per-path evaluation -- the table when the launch needs every time index about twice
+// (from 3e7 camera samples on, a 1080p frame at 16 spp: the build costs what 1.7e7 evaluations cost, but takes 1.9 GB per moving instance), for every later
+// launch of the frame and the frames of a sequence that rendered through it, or as tray_scene_set_transform_table says; 2. the chosen one exists (else
+// the other serves); 3. the pool, kept or as large as the budget grants, halved while hipMalloc refuses (fragmentation, another scene's pool) down to
+// 64 chunks, then TRAY_E_NOMEM with the handle as it was; 4. s->launch_dev: `dev` with the cache, or the table in its place.
+#ifndef XF_TABLE_MIN_SAMPLES
+#define XF_TABLE_MIN_SAMPLES 30000000ull
+#endif
+static int launch_prepare(TrayDeviceScene* s, uint64_t samples, hipStream_t stream) {
+    LaunchBuffers& b = s->lb;
+    b.last_used_table = false;
+    const uint32_t stride = s->dev.n_moving + (s->camera_animated ? 1u : 0u);
+    bool table = false;
+    if (s->animated && stride != 0u) {
+        int want = s->xf_table_req;
+        if (const char* e = getenv("TRAYHIP_XF_TABLE")) want = atoi(e) != 0 ? 1 : 0;
+        if (want < 0) want = (samples >= XF_TABLE_MIN_SAMPLES || b.xf_table_built || b.d_xf_table) ? 1 : 0;
+        int rc = want ? TRAY_E_NOMEM : xf_cache_ensure(s);
+        if (rc == TRAY_E_NOMEM) {   // (the table wanted, or no room for the cache: the table is smaller from a few million slots on)
+            rc = xf_table_ensure(s, stride, stream);
+            table = rc == TRAY_OK;
+            if (rc == TRAY_E_NOMEM) rc = xf_cache_ensure(s);
+        }
+        if (rc != TRAY_OK) return rc;
     }
-    s->last_used_table = true;
+    b.last_used_table = table;
+    const bool reads_cache = s->wavefront && !table && s->dev.n_moving != 0u;   // (the tile kernel's cache has a column per resident thread: lb_fit)
+    if (s->wavefront && !s->narrow_trees) { set_error("wavefront schedule: a BVH of more than 8 388 607 nodes or triangles (the traversal keeps a node as a 32-bit descriptor)"); return TRAY_E_UNSUPPORTED; }
+    if (s->wavefront && !s->ordered_boxes) { set_error("wavefront schedule: a BVH box with min > max (or NaN) on some axis; TRAYHIP_MODE=mega renders such a scene with the tile kernel"); return TRAY_E_UNSUPPORTED; }
+    if (s->wavefront && !b.wf.ready) {
+        uint32_t n_slots = reads_cache ? std::min(b.xf_cache_lanes, wf_slot_wish(s, s->wf_req_slots)) : wf_slot_count(s);
+        for (;;) {
+            const int rc = wf_alloc(s, n_slots);
+            if (rc == TRAY_OK) break;
+            if (rc != TRAY_E_NOMEM) return rc;
+            if (n_slots / 2u < 64u * TR_BLOCK) {
+                set_error("the wavefront schedule's buffers could not be allocated even for " + std::to_string(n_slots) + " pool slots (" +
+                          std::to_string((n_slots * wf_bytes_per_slot()) >> 20) + " MiB): " + tray_last_error());
+                return TRAY_E_NOMEM;
+            }
+            n_slots = n_slots / 2u / TR_BLOCK * TR_BLOCK;
+            b.wf_shrunk = true;
+        }
+    }
+    // the stage kernels index the per-path cache by pool slot: it must have a record for every slot
+    if (reads_cache && (!b.xf_cache || b.wf.pool.n_slots > b.xf_cache_lanes)) {
+        set_error("wavefront schedule: " + std::to_string(b.wf.pool.n_slots) + " pool slots but a per-path transform cache of " + std::to_string(b.xf_cache ? b.xf_cache_lanes : 0u) + " paths");
+        return TRAY_E_DEVICE;
+    }
+    DevScene& d = s->launch_dev;
+    d = s->dev;
+    d.xf_cache = b.xf_cache; d.xf_cache_lanes = b.xf_cache_lanes;
+    if (table) { d.xf_tab = b.d_xf_table; d.xf_tab_stride = b.xf_table_stride; }
+    if (table && s->wavefront) {   // the stage kernels index the table by the path's time index; the tile kernel keeps its cache columns and fills them from it
+        d.xf_cache = b.d_xf_table; d.xf_table = 1u; d.xf_aos = 1u; d.xf_stride = b.xf_table_stride;
+    }
     return TRAY_OK;
 }
 
@@ -1289,19 +1287,20 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     kf = mix(kf + s->dev.frame);
     if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream);
     s->last_was_wavefront = false;
+    const bool had_pool = s->lb.wf.ready;
     {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = xf_table_prepare(s, (uint64_t)tile_count * 64u * spp, stream);
-        if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] transform table / cache prepared in %.1f ms (table %s, %u of %u records per index in use)\n",
-                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), s->last_used_table ? "on" : "off", s->xf_table_stride, s->xf_table_cap);
+        const int rc = launch_prepare(s, (uint64_t)tile_count * 64u * spp, stream);
+        if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] launch buffers prepared in %.1f ms (table %s, %u of %u records per index in use; pool %s: %u slots)\n",
+                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), s->lb.last_used_table ? "on" : "off",
+                                             s->lb.xf_table_stride, s->lb.xf_table_cap, had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
         if (rc != TRAY_OK) return rc;
     }
     if (s->wavefront) {
         const auto t0 = std::chrono::steady_clock::now();
-        const bool had_pool = s->wf_ready;
         const int rc = launch_wavefront(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] wavefront launch enqueued in %.1f ms (pool %s: %u slots)\n",
-                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->pool.n_slots);
+                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
         return rc;
     }
     // Items per tile (k_path_tiles: progressive slices, level-major: the launch ends with its smallest items). A slice costs its own film resolve and
@@ -1581,13 +1580,13 @@ int tray_multi_set_transform_table(TrayMultiScene* m, int mode) {
 int tray_debug_transform_table(TrayDeviceScene* s, uint32_t n, uint32_t* n_differ) {
     if (!s || !n_differ) { set_error("tray_debug_transform_table: null argument"); return TRAY_E_INVALID; }
     *n_differ = 0;
-    if (!s->d_xf_table || !s->xf_table_built) { set_error("tray_debug_transform_table: this frame has no transform table (no launch wanted one yet)"); return TRAY_E_INVALID; }
+    if (!s->lb.d_xf_table || !s->lb.xf_table_built) { set_error("tray_debug_transform_table: this frame has no transform table (no launch wanted one yet)"); return TRAY_E_INVALID; }
     HIP_CHECK(hipSetDevice(s->device));
     uint32_t* d_bad = nullptr;
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_bad), sizeof(uint32_t)));
     hipError_t e = hipMemset(d_bad, 0, sizeof(uint32_t));
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_xf_table_check, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, nullptr, s->dev, s->d_xf_table, s->xf_table_stride, n, d_bad);
+        hipLaunchKernelGGL(k_xf_table_check, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, nullptr, s->dev, s->lb.d_xf_table, s->lb.xf_table_stride, n, d_bad);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(n_differ, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost);
@@ -1600,13 +1599,13 @@ int tray_scene_set_wavefront(TrayDeviceScene* s, uint32_t pool_slots, uint32_t v
     if (s->broken) { set_error("tray_scene_set_wavefront: the handle is only good for tray_scene_destroy after a failed frame update"); return TRAY_E_INVALID; }
     if (views > (uint32_t)WF_PIPES_MAX) { set_error("tray_scene_set_wavefront: at most " + std::to_string(WF_PIPES_MAX) + " views"); return TRAY_E_INVALID; }
     if (slices > WF_MAX_SLICES || (slices & (slices - 1u)) != 0u) { set_error("tray_scene_set_wavefront: slices per tile must be 0 or a power of two up to " + std::to_string(WF_MAX_SLICES)); return TRAY_E_INVALID; }
-    const uint32_t before = wf_slot_wish(s);
+    const uint32_t before = wf_slot_wish(s, s->wf_req_slots);
     s->wf_req_slots = pool_slots; s->wf_req_views = views; s->wf_req_slices = slices;
-    if (s->wf_ready && wf_slot_wish(s) != before) {   // another pool size: the buffers go, the next render call allocates them anew
+    if (s->lb.wf.ready && wf_slot_wish(s, s->wf_req_slots) != before) {   // another pool size: the buffers go, the next render call allocates them anew
         HIP_CHECK(hipSetDevice(s->device));
         HIP_CHECK(hipDeviceSynchronize());
-        wf_free(s);
-        s->wf_shrunk = false;
+        lb_drop(s->lb, LB_POOL);
+        s->lb.wf_shrunk = false;
     }
     return TRAY_OK;
 }
@@ -1623,16 +1622,16 @@ int tray_last_schedule(TrayDeviceScene* s, TrayScheduleInfo* out) {
     std::memset(out, 0, sizeof *out);
     out->wavefront = s->wavefront ? 1u : 0u;
     out->launched_wavefront = s->last_was_wavefront ? 1u : 0u;
-    out->pool_slots = s->pool.n_slots; out->chunks = s->n_chunks;
+    out->pool_slots = s->lb.wf.pool.n_slots; out->chunks = s->lb.wf.n_chunks;
     out->views = s->last_was_wavefront ? s->last_views : 0u; out->slices = s->last_was_wavefront ? s->last_slices : 0u;
-    out->pool_bytes = s->pool.data ? (uint64_t)F_COUNT * s->pool.n_slots * sizeof(float) : 0u;
-    out->schedule_bytes = s->pool.data ? (uint64_t)s->pool.n_slots * wf_bytes_per_slot() : 0u;
-    out->xf_cache_bytes = s->xf_cache_bytes;
+    out->pool_bytes = s->lb.wf.pool.data ? (uint64_t)F_COUNT * s->lb.wf.pool.n_slots * sizeof(float) : 0u;
+    out->schedule_bytes = s->lb.wf.pool.data ? (uint64_t)s->lb.wf.pool.n_slots * wf_bytes_per_slot() : 0u;
+    out->xf_cache_bytes = s->lb.xf_cache_bytes;
     out->n_moving = s->dev.n_moving;
     out->tile_workgroups = (uint32_t)s->n_blocks;
-    out->transform_table = s->last_used_table ? 1u : 0u;
+    out->transform_table = s->lb.last_used_table ? 1u : 0u;
     out->binned_stages = (s->last_was_wavefront && WF_FOLD_C) ? s->wf_bin_stages : 0u;
-    out->xf_table_bytes = s->d_xf_table ? ((uint64_t)1 << 24) * s->xf_table_cap * TR_XF_REC * sizeof(float) : 0u;   // (the buffer: sized for what any frame of the sequence can move)
+    out->xf_table_bytes = s->lb.d_xf_table ? ((uint64_t)1 << 24) * s->lb.xf_table_cap * TR_XF_REC * sizeof(float) : 0u;   // (the buffer: sized for what any frame of the sequence can move)
     return TRAY_OK;
 }
 

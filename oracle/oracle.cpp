@@ -892,5 +892,28 @@ void oracle_film_write(const TrayFlatScene* fs, uint32_t n, const float* samples
     for (uint32_t i = 0; i < n; ++i) { v[i].x = samples5[5 * i]; v[i].y = samples5[5 * i + 1]; v[i].c = Colorf(samples5[5 * i + 2], samples5[5 * i + 3], samples5[5 * i + 4]); }
     film_write(fs->film, v, tile_x * 8, tile_y * 8, rgbw, 0, 0, (int)fs->film.width);
 }
+// RenderTarget::write of each sample of tile (tile_x, tile_y) on its own: out[i] = the RGBW pixels [floor(x) - r, floor(x) + r] x
+// [floor(y) - r, floor(y) + r] of an image that holds that sample alone (zero off the image). Returns -1 if a sample wrote outside its patch.
+int oracle_film_patches(const TrayFilm* film, uint32_t n, const float* samples5, uint32_t tile_x, uint32_t tile_y, int r, float* out) {
+    const int W = (int)film->width, H = (int)film->height, P = 2 * r + 1;
+    std::vector<float> img((size_t)W * H * 4, 0.0f);
+    std::vector<ImageSample> v(1);
+    for (uint32_t i = 0; i < n; ++i) {
+        v[0].x = samples5[5 * i]; v[0].y = samples5[5 * i + 1]; v[0].c = Colorf(samples5[5 * i + 2], samples5[5 * i + 3], samples5[5 * i + 4]);
+        film_write(*film, v, tile_x * 8, tile_y * 8, img.data(), 0, 0, W);
+        const int cx = (int)std::floor(v[0].x), cy = (int)std::floor(v[0].y);
+        float* o = out + (size_t)i * P * P * 4;
+        for (int py = 0; py < P; ++py)
+            for (int px = 0; px < P; ++px) {
+                const int ix = cx - r + px, iy = cy - r + py;
+                for (int k = 0; k < 4; ++k) o[(py * P + px) * 4 + k] = 0.0f;
+                if (ix < 0 || iy < 0 || ix >= W || iy >= H) continue;
+                float* src = img.data() + ((size_t)iy * W + ix) * 4;
+                for (int k = 0; k < 4; ++k) { o[(py * P + px) * 4 + k] = src[k]; src[k] = 0.0f; }
+            }
+    }
+    for (float x : img) if (x != 0.0f) return -1;
+    return 0;
+}
 
 }  // extern "C"

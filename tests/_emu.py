@@ -72,6 +72,8 @@ def emu(defines=()):
         h.emu_retraced.restype = C.c_uint
         h.emu_wf_bin.restype = C.c_uint32
         h.emu_wf_bin.argtypes = [C.c_uint32] + [C.c_void_p] * 6 + [C.c_int]
+        h.emu_film_splat.restype = C.c_int
+        h.emu_film_splat.argtypes = [C.POINTER(L.TrayFilm), C.c_int] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
         _libs[key] = h
     return _libs[key]
 
@@ -146,6 +148,22 @@ def render_wavefront(flat, tiles_xy, spp, seed, trace=0, n_chunks=4, trace_block
                                          lds_depth, stats.ctypes.data)
     assert rc == 0, f"emu_render_wavefront: {rc}"
     return img, tuple(int(x) for x in stats)
+
+
+FILM_PATCH_R = 6   # emu_kernels.cpp: EMU_PATCH_R
+
+
+def film_splat(film, mode, tile, samples, group=(1, 1)):
+    """emu_film_splat: each of `samples` ((n, 5): x, y, r, g, b of samples of `tile`) through one device film on its own; returns the
+    (n, 13, 13, 4) RGBW pixels around each sample's pixel, or None if the film has no row bins (modes 2, 3)"""
+    samples = np.ascontiguousarray(samples, np.float32).reshape(-1, 5)
+    p = 2 * FILM_PATCH_R + 1
+    out = np.zeros((len(samples), p, p, 4), np.float32)
+    rc = emu().emu_film_splat(C.byref(film), mode, tile[0], tile[1], group[0], group[1], len(samples), samples.ctypes.data, out.ctypes.data)
+    if rc == 1:
+        return None
+    assert rc == 0, f"emu_film_splat(mode {mode}, tile {tile}, group {group}): {rc} (-1: a write outside the sample's patch or a window)"
+    return out
 
 
 def wf_bin(n_chunks, counts, rays, bmin, bmax, stage=0):

@@ -88,8 +88,21 @@ def oracle():
         o.oracle_texture_sample.argtypes = [FS, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         o.oracle_film_write.restype = None
         o.oracle_film_write.argtypes = [FS, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        o.oracle_film_patches.restype = C.c_int
+        o.oracle_film_patches.argtypes = [C.POINTER(L.TrayFilm), C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         _o = o
     return _o
+
+
+def film_patches(film, tile, samples, r):
+    """oracle_film_patches: RenderTarget::write of each sample ((n, 5): x, y, r, g, b) of `tile` on its own; the (n, 2r+1, 2r+1, 4) RGBW
+    pixels around each sample's pixel"""
+    samples = np.ascontiguousarray(samples, np.float32).reshape(-1, 5)
+    p = 2 * r + 1
+    out = np.zeros((len(samples), p, p, 4), np.float32)
+    rc = oracle().oracle_film_patches(C.byref(film), len(samples), samples.ctypes.data, tile[0], tile[1], r, out.ctypes.data)
+    assert rc == 0, "oracle_film_patches: a sample wrote outside its patch"
+    return out
 
 
 def render_tiles(flat, spp, seed=1, tile_start=0, tile_count=0, stride=1, threads=None, flags=0):

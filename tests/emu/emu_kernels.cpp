@@ -663,6 +663,98 @@ uint32_t emu_wf_bin(uint32_t n_chunks, const uint32_t* counts, const uint32_t* q
     return pool.seg_cap;
 }
 
+// The device films (kernels.hip) for samples of ONE tile (tx, ty), each sample written on its own into a zeroed image, and the
+// image's pixels [floor(sx) - EMU_PATCH_R, floor(sx) + EMU_PATCH_R] x (the same in y) copied to out[i] (RGBW, zero off the image):
+//   mode 0  film_splat into k_path_tiles' LDS window, flushed as k_path_tiles flushes it (TRAYHIP_DIRECT_FILM)
+//   mode 1  film_splat_global (the wavefront film for filters without row bins; class-boundary samples of the row-binned films)
+//   mode 2  film_splat_rows into the row bins, film_resolve_rows, the flush (k_path_tiles' row-binned film); 1 if the film has no row bins
+//   mode 3  film_splat_rows_global<false> (the wavefront's row bins in global memory), film_resolve_rows, the flush; 1 as mode 2
+//   mode 4  film_splat_window under the window of a group of group_w x group_h tiles aligned to multiples of the group (clipped to the
+//           image's tiles, as the box of a ragged last group is), flushed as k_sampler_pass flushes it
+// Returns 0; -1 if a write landed outside every patch or in the guard zones around the windows (an out-of-bounds LDS write on the device).
+#define EMU_PATCH_R 6
+int emu_film_splat(const TrayFilm* film, int mode, uint32_t tx, uint32_t ty, uint32_t group_w, uint32_t group_h, uint32_t n, const float* samples5, float* out) {
+    DevScene d;
+    std::memset(&d, 0, sizeof d);
+    d.width = film->width; d.height = film->height;
+    d.filter_w = film->filter_w; d.filter_h = film->filter_h; d.inv_w = film->inv_w; d.inv_h = film->inv_h;
+    d.fpw = film->filter_pixel_w; d.fph = film->filter_pixel_h;
+    d.filter_table = film->table; d.filter_x = film->table_x; d.filter_y = film->table_y;
+    TrayFlatScene fs;
+    std::memset(&fs, 0, sizeof fs);
+    fs.film = *film;
+    if ((mode == 2 || mode == 3) && !film_rows_ok(&fs)) return 1;
+    const int W = (int)film->width, H = (int)film->height, x0 = (int)tx * 8, y0 = (int)ty * 8;
+    const size_t guard = 4096;
+    std::vector<float> img((size_t)W * H * 4, 0.0f), win(guard + 4 * WIN_PLANE + guard, 0.0f), gwin(guard + 4 * SP_WIN_MAX * SP_WIN_MAX + guard, 0.0f);
+    std::vector<float> bins(guard + ROWBIN_SIZE + guard, 0.0f);
+    float* const s_win = win.data() + guard;
+    float* const s_bins = bins.data() + guard;
+    float* const s_gwin = gwin.data() + guard;
+    // the group's window (k_sampler_pass: the box of its tiles, the filter's halo around it)
+    const int ntx = W / 8, nty = H / 8;
+    const int gx0 = (int)(tx / group_w * group_w), gy0 = (int)(ty / group_h * group_h);
+    const int gx1 = std::min(gx0 + (int)group_w, ntx) - 1, gy1 = std::min(gy0 + (int)group_h, nty) - 1;
+    const int gwx0 = gx0 * 8 - d.fpw, gwy0 = gy0 * 8 - d.fph;
+    const int gww = (gx1 - gx0 + 1) * 8 + 2 * d.fpw + 1, gwh = (gy1 - gy0 + 1) * 8 + 2 * d.fph + 1;
+    if (mode == 4 && (gww > SP_WIN_MAX || gwh > SP_WIN_MAX)) return -2;
+    // flush of k_path_tiles' window (kernels.hip, after the tile's paths)
+    auto flush_tile = [&]() {
+        const int wx0 = x0 - d.fpw, wy0 = y0 - d.fph, ww = 8 + 2 * d.fpw + 1, wh = 8 + 2 * d.fph + 1;
+        for (int i = 0; i < ww * wh; ++i) {
+            const int wy = i / ww, wx = i - wy * ww, ix = wx0 + wx, iy = wy0 + wy;
+            if (ix < 0 || iy < 0 || ix >= W || iy >= H) continue;
+            const int o = wy * WIN_STRIDE + wx;
+            float* dst = img.data() + ((size_t)iy * W + ix) * 4;
+            for (int k = 0; k < 4; ++k) dst[k] += s_win[o + k * WIN_PLANE];
+        }
+        std::memset(s_win, 0, 4 * WIN_PLANE * sizeof(float));
+    };
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* s = samples5 + 5 * i;
+        const float sx = s[0], sy = s[1];
+        const f3 c = mk(s[2], s[3], s[4]);
+        if (mode == 0) {
+            film_splat(d, s_win, film->table, x0, y0, sx, sy, c);
+            flush_tile();
+        } else if (mode == 1) {
+            film_splat_global(d, img.data(), film->table, x0, y0, sx, sy, c);
+        } else if (mode == 2 || mode == 3) {
+            const int py_l = (int)floorf(sy) - y0;
+            if (mode == 2) film_splat_rows(d, s_bins, film->table_x, img.data(), film->table, x0, y0, py_l, sx, sy, c);
+            else film_splat_rows_global<false>(d, s_bins, film->table_x, img.data(), film->table, x0, y0, py_l, sx, sy, c);
+            for (uint32_t tid = 0; tid < TR_BLOCK; ++tid) film_resolve_rows(d, s_bins, film->table_y, s_win, y0, tid);
+            std::memset(s_bins, 0, ROWBIN_SIZE * sizeof(float));
+            flush_tile();
+        } else if (mode == 4) {
+            film_splat_window(d, s_gwin, gwx0, gwy0, gww, film->table, x0, y0, sx, sy, c);
+            for (int k = 0; k < gww * gwh; ++k) {   // (k_sampler_pass's flush)
+                const int wy = k / gww, wx = k - wy * gww, ix = gwx0 + wx, iy = gwy0 + wy;
+                if (ix < 0 || iy < 0 || ix >= W || iy >= H) continue;
+                float* dst = img.data() + ((size_t)iy * W + ix) * 4;
+                for (int q = 0; q < 4; ++q) dst[q] += s_gwin[4 * k + q];
+            }
+            std::memset(s_gwin, 0, 4 * SP_WIN_MAX * SP_WIN_MAX * sizeof(float));
+        } else {
+            return -3;
+        }
+        const int cx = (int)floorf(sx), cy = (int)floorf(sy), P = 2 * EMU_PATCH_R + 1;
+        float* o = out + (size_t)i * P * P * 4;
+        std::memset(o, 0, (size_t)P * P * 4 * sizeof(float));
+        for (int py = 0; py < P; ++py)
+            for (int px = 0; px < P; ++px) {
+                const int ix = cx - EMU_PATCH_R + px, iy = cy - EMU_PATCH_R + py;
+                if (ix < 0 || iy < 0 || ix >= W || iy >= H) continue;
+                float* src = img.data() + ((size_t)iy * W + ix) * 4;
+                for (int k = 0; k < 4; ++k) { o[(py * P + px) * 4 + k] = src[k]; src[k] = 0.0f; }
+            }
+    }
+    for (float v : img) if (v != 0.0f) return -1;
+    for (const std::vector<float>* b : {&win, &gwin, &bins})
+        for (size_t k = 0; k < b->size(); ++k) if ((*b)[k] != 0.0f) return -1;
+    return 0;
+}
+
 }  // extern "C"
 
 // The device order of the trees and the wavefront traversal's instance records, as tray_scene_create uploads them (host/gates.hpp), for

@@ -521,9 +521,25 @@ def test_tr15_stand_in_image_rmse(tmp_path):
     assert r < 1e-4
 
 
-@pytest.mark.parametrize("filt", [{"type": "gaussian", "width": 1.5, "height": 1.5, "alpha": 2.0},
-                                  {"type": "gaussian", "width": 2.0, "height": 2.0, "alpha": 1.0},
-                                  {"type": "mitchell_netravali", "width": 1.0, "height": 2.0, "b": 0.2, "c": 0.4}])
+def weight_rel(gpu, cpu):
+    """per pixel |w_gpu - w_oracle| / |w_oracle| over the pixels the oracle wrote. The weight plane does not depend on radiance: with the
+    sample positions bit-identical only the order of the f32 sums differs (the host emulation of the same kernels measures at most 5.3e-6);
+    a footprint one column or row off gives 5e-4 and more (tests/test_film_footprints.py)."""
+    t = cpu[..., 3] != 0
+    assert ((gpu[..., 3] != 0) == t).all(), "touched pixels differ"
+    return float((np.abs(gpu[..., 3] - cpu[..., 3])[t] / np.abs(cpu[..., 3][t])).max())
+
+
+FILTER_GRID = [{"type": "gaussian", "width": 1.5, "height": 1.5, "alpha": 2.0},
+               {"type": "gaussian", "width": 2.0, "height": 2.0, "alpha": 1.0},
+               {"type": "mitchell_netravali", "width": 1.0, "height": 2.0, "b": 0.2, "c": 0.4},
+               {"type": "mitchell_netravali", "width": 1.9, "height": 1.9, "b": 1 / 3, "c": 1 / 3},
+               {"type": "mitchell_netravali", "width": 2.25, "height": 2.0, "b": 1 / 3, "c": 1 / 3},
+               {"type": "gaussian", "width": 2.49, "height": 2.49, "alpha": 2.0},
+               {"type": "gaussian", "width": 1.9, "height": 2.25, "alpha": 2.0}]
+
+
+@pytest.mark.parametrize("filt", FILTER_GRID[:3])
 def test_other_reconstruction_filters(filt, tmp_path):
     """Gaussian (film/filter/gaussian.rs) and non-default footprints: widths other than 2 take the verbatim
     RenderTarget::write path instead of the row-binned film."""
@@ -533,8 +549,62 @@ def test_other_reconstruction_filters(filt, tmp_path):
     gpu, tim = gpu_render(scene, rt, 16, fi, seed=8)
     cpu, st = O.render_tiles(scene.flatten(0), 16, seed=8)
     assert tim.samples == st.samples
+    assert weight_rel(gpu, cpu) <= 2e-5
     assert np.abs(gpu[..., 3] - cpu[..., 3]).max() < 1e-3 * cpu[..., 3].max()
     assert rmse(gpu, cpu) < 1e-4
+
+
+@pytest.mark.parametrize("film", ["tiles", "wave", "direct"])
+@pytest.mark.parametrize("filt", FILTER_GRID, ids=lambda f: f"{f['type'][:5]}-{f['width']}x{f['height']}")
+def test_reconstruction_filter_footprints(filt, film, tmp_path, monkeypatch):
+    """Gaussian (film/filter/gaussian.rs) and footprints other than 2 x 2, up to the widest the film windows hold (floor(2 w) <= 4), through
+    the tile kernel (the row-binned film where h = 2), the wavefront schedule and the tile kernel's direct film (TRAYHIP_DIRECT_FILM):
+    RenderTarget::write's footprint exactly (per-pixel weight bar)."""
+    if film == "wave":
+        monkeypatch.setenv("TRAYHIP_MODE", "wave")
+    if film == "direct":
+        monkeypatch.setenv("TRAYHIP_DIRECT_FILM", "1")
+    d = scenes.cornell_box(96, 64, 16)
+    d["film"]["filter"] = filt
+    scene, rt, _, fi = load(d, tmp_path)
+    gpu, tim = gpu_render(scene, rt, 16, fi, seed=8)
+    cpu, st = O.render_tiles(scene.flatten(0), 16, seed=8)
+    assert tim.samples == st.samples
+    wr = weight_rel(gpu, cpu)
+    print(f"{film} {filt['type']} {filt['width']}x{filt['height']}: per-pixel relative weight difference {wr:.2e}, RMSE {rmse(gpu, cpu):.2e}")
+    assert wr <= 2e-5
+    assert np.abs(gpu[..., 3] - cpu[..., 3]).max() < 1e-3 * cpu[..., 3].max()
+    assert rmse(gpu, cpu) < 1e-4
+
+
+@pytest.mark.parametrize("filt", FILTER_GRID[3:], ids=lambda f: f"{f['type'][:5]}-{f['width']}x{f['height']}")
+def test_other_reconstruction_filters_under_other_samplers(filt, tmp_path):
+    """k_sampler_pass's film (film_splat_window, clipped to each sample's own tile) at the footprints where RenderTarget::write's lock-block
+    test binds: Uniform (pixel centres) and Adaptive(4, 4) (positions all over the pixel; min = max, so no decision can flip a count)."""
+    d = scenes.cornell_box(96, 64, 4)
+    d["film"]["filter"] = filt
+    scene, rt, _, fi = load(d, tmp_path)
+    flat = scene.flatten(0)
+    for name, make, kind, args in (("uniform", lambda dim, spp: T.sampler.Uniform(dim), O.SAMPLER_UNIFORM, ()),
+                                   ("adaptive(4, 4)", lambda dim, spp: T.sampler.Adaptive(dim, 4, 4), O.SAMPLER_ADAPTIVE, (4, 4))):
+        gpu, tim = gpu_render_sampler(scene, rt, make, fi, seed=4)
+        cpu, st, _ = O.render_tiles_sampler(flat, kind, *args, seed=4)
+        assert tim.samples == st.samples
+        wr = weight_rel(gpu, cpu)
+        print(f"{name} {filt['type']} {filt['width']}x{filt['height']}: per-pixel relative weight difference {wr:.2e}, RMSE {rmse(gpu, cpu):.2e}")
+        assert wr <= 2e-5
+        assert np.abs(gpu[..., 3] - cpu[..., 3]).max() < 1e-3 * cpu[..., 3].max()
+
+
+def test_filters_too_wide_for_the_film_window_are_refused(tmp_path):
+    """floor(2 w) > 4 does not fit the film windows' 4-pixel halo: tray_scene_create refuses it, on either axis"""
+    for w, h in ((2.5, 2.0), (2.0, 2.5)):
+        d = scenes.cornell_box(32, 24, 1)
+        d["film"]["filter"] = {"type": "mitchell_netravali", "width": w, "height": h, "b": 1 / 3, "c": 1 / 3}
+        scene, *_ = load(d, tmp_path)
+        with pytest.raises(T.TrayError) as e:
+            scene.device_scene(0, 0)
+        assert e.value.code == L.TRAY_E_UNSUPPORTED and "2.5" in e.value.message
 
 
 @pytest.mark.parametrize("name", list(SCENES))

@@ -439,12 +439,10 @@ static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDevic
         set_error("Image dimensions not evenly divided by blocks of (8, 8)");
         return TRAY_E_INVALID;
     }
+    // the film windows (WIN_MAX, ROW_W, SP_WIN_MAX) hold a tile's write range with a 4-pixel halo: filter widths below 2.5. Every device
+    // film writes within the write range of the sample's tile (kernels.hip: film_admit), so any width with floor(2 w) <= 4 fits.
     if (f->film.filter_pixel_w > 4 || f->film.filter_pixel_h > 4 || f->film.filter_pixel_w < 0 || f->film.filter_pixel_h < 0) {
-        set_error("reconstruction filters wider than 2 px are not supported by the LDS film window");
-        return TRAY_E_UNSUPPORTED;
-    }
-    if (f->film.filter_w > 2.0f || f->film.filter_h > 2.0f) {
-        set_error("reconstruction filters wider than 2.0 are not supported by the LDS film window");
+        set_error("reconstruction filters of width or height 2.5 and more are not supported by the LDS film window");
         return TRAY_E_UNSUPPORTED;
     }
     if (f->integrator > TRAY_INTEGRATOR_WHITTED) { set_error("unknown integrator"); return TRAY_E_INVALID; }

@@ -50,6 +50,22 @@ using namespace tr;
 
 struct DevStats { unsigned long long samples, vertices, rays, trav[18]; };   // trav[stage * 6 + k]: traversal counters of builds with -DWF_TRACE_STATS
 
+// RenderTarget::write's footprint on one axis (render_target.rs:77-109). A sample at s of the tile whose write range is [r0, r1] (the
+// tile widened by fp pixels and clipped to the image) reaches pixel i of that range only if i's 2-pixel lock block, clipped to the range,
+// [b0, b1) admits it: b0 - fp <= s < b1 + fp. The test is separable (a 2 x 2 block admits a sample iff both of its axes do), and both block
+// bounds rise with i, so the admitted pixels are one run [lo, hi]: hi is the last pixel whose block starts at or before floor(s) + fp,
+// lo the first whose block ends after floor(s) - fp (blocks start at even pixels). At most 2 fp + 2 pixels, as many as the old
+// [floor(s - 1/2) - fp, floor(s - 1/2) + fp + 1]. The two differ -- by one column or row at a time, either way -- for the footprints
+// with w^2 > fp + 1/2 (w = 1.9, 2.25, ...: the filter's |i - s + 1/2| <= w^2 test reaches past the block's bound); at w = 1, 1.5, 2 the
+// filter test alone decides.
+// s lies in its tile, [x0, x0 + 8] (the upper end: a pixel position px + u that rounds up in f32), so floor(s) + fp >= r0 and
+// floor(s) - fp <= r1: the run is never cut off by the far end of the range, and the two clips below are all the range needs.
+TR_DEV void film_admit(float s, int r0, int r1, int fp, int& lo, int& hi) {
+    const int m = (int)floorf(s) + fp;
+    hi = min(r1, m | 1);
+    lo = max(r0, (m - 2 * fp) & ~1);
+}
+
 // RenderTarget::write for one sample into the LDS window (render_target.rs:118-146).
 // win origin = (x0 - fpw, y0 - fph); ranges already clipped to the image.
 __device__ __forceinline__ void film_splat(const DevScene& sc, float* __restrict__ s_win, const float* __restrict__ s_table,
@@ -58,9 +74,9 @@ __device__ __forceinline__ void film_splat(const DevScene& sc, float* __restrict
     const int xr0 = max(x0 - fpw, 0), xr1 = min(x0 + 8 + fpw, (int)sc.width - 1);
     const int yr0 = max(y0 - fph, 0), yr1 = min(y0 + 8 + fph, (int)sc.height - 1);
     const float img_x = sx - 0.5f, img_y = sy - 0.5f;
-    const int bx = (int)floorf(img_x), by = (int)floorf(img_y);
-    const int ix_lo = max(xr0, bx - fpw), ix_hi = min(xr1, bx + fpw + 1);
-    const int iy_lo = max(yr0, by - fph), iy_hi = min(yr1, by + fph + 1);
+    int ix_lo, ix_hi, iy_lo, iy_hi;
+    film_admit(sx, xr0, xr1, fpw, ix_lo, ix_hi);
+    film_admit(sy, yr0, yr1, fph, iy_lo, iy_hi);
     const int wx0 = x0 - fpw, wy0 = y0 - fph;
     for (int iy = iy_lo; iy <= iy_hi; ++iy) {
         float fy = fabsf((float)iy - img_y) * sc.inv_h;
@@ -103,8 +119,8 @@ __device__ __forceinline__ void film_splat_rows(const DevScene& sc, float* __res
     const int cy = (int)fl8 + 4;
     const int fpw = sc.fpw;
     const int xr0 = max(x0 - fpw, 0), xr1 = min(x0 + 8 + fpw, (int)sc.width - 1);
-    const int bx = (int)floorf(img_x);
-    const int ix_lo = max(xr0, bx - fpw), ix_hi = min(xr1, bx + fpw + 1);
+    int ix_lo, ix_hi;
+    film_admit(sx, xr0, xr1, fpw, ix_lo, ix_hi);   // (y: film_resolve_rows; with h = 2 the block test never binds: h^2 = 4 <= fph + 1/2)
     const int wx0 = x0 - fpw;
     float* __restrict__ row = s_rowbin + (py_l * 8 + cy) * ROW_W * 4;
     for (int ix = ix_lo; ix <= ix_hi; ++ix) {
@@ -159,9 +175,9 @@ __device__ __forceinline__ void film_splat_global(const DevScene& sc, float* __r
     const int xr0 = max(x0 - fpw, 0), xr1 = min(x0 + 8 + fpw, (int)sc.width - 1);
     const int yr0 = max(y0 - fph, 0), yr1 = min(y0 + 8 + fph, (int)sc.height - 1);
     const float img_x = sx - 0.5f, img_y = sy - 0.5f;
-    const int bx = (int)floorf(img_x), by = (int)floorf(img_y);
-    const int ix_lo = max(xr0, bx - fpw), ix_hi = min(xr1, bx + fpw + 1);
-    const int iy_lo = max(yr0, by - fph), iy_hi = min(yr1, by + fph + 1);
+    int ix_lo, ix_hi, iy_lo, iy_hi;
+    film_admit(sx, xr0, xr1, fpw, ix_lo, ix_hi);
+    film_admit(sy, yr0, yr1, fph, iy_lo, iy_hi);
     for (int iy = iy_lo; iy <= iy_hi; ++iy) {
         float fy = fabsf((float)iy - img_y) * sc.inv_h;
         if (fy > sc.filter_h) continue;
@@ -192,8 +208,8 @@ __device__ __forceinline__ void film_splat_rows_global(const DevScene& sc, float
     const int cy = (int)fl8 + 4;
     const int fpw = sc.fpw;
     const int xr0 = max(x0 - fpw, 0), xr1 = min(x0 + 8 + fpw, (int)sc.width - 1);
-    const int bx = (int)floorf(img_x);
-    const int ix_lo = max(xr0, bx - fpw), ix_hi = min(xr1, bx + fpw + 1);
+    int ix_lo, ix_hi;
+    film_admit(sx, xr0, xr1, fpw, ix_lo, ix_hi);   // (y: film_resolve_rows; with h = 2 the block test never binds: h^2 = 4 <= fph + 1/2)
     const int wx0 = x0 - fpw;
     float* __restrict__ row = bins + (py_l * 8 + cy) * ROW_W * 4;
     for (int ix = ix_lo; ix <= ix_hi; ++ix) {
@@ -578,14 +594,18 @@ struct SamplerPass {
     uint32_t min_spp, max_spp, step;
     uint32_t lum_cap;       // luminance slots per pixel
 };
-// RenderTarget::write of one sample into an LDS window of ww x wh pixels (RGBW interleaved) whose pixel (0, 0) is image pixel (wx0, wy0): render_target.rs:118-146
-// with the image's bounds as the only clip -- the window of a group of tiles covers every footprint of a sample inside them
-TR_DEV void film_splat_window(const DevScene& sc, float* __restrict__ s_win, int wx0, int wy0, int ww, const float* __restrict__ table, float sx, float sy, f3 c) {
+// RenderTarget::write of one sample of the tile at (x0, y0) into an LDS window of ww x wh pixels (RGBW interleaved) whose pixel (0, 0) is
+// image pixel (wx0, wy0): render_target.rs:77-146. The sample is clipped to ITS tile's write range, as the reference writes it per tile; that
+// range lies inside the window of any group of tiles that holds the tile.
+TR_DEV void film_splat_window(const DevScene& sc, float* __restrict__ s_win, int wx0, int wy0, int ww, const float* __restrict__ table,
+                              int x0, int y0, float sx, float sy, f3 c) {
     const int fpw = sc.fpw, fph = sc.fph;
+    const int xr0 = max(x0 - fpw, 0), xr1 = min(x0 + 8 + fpw, (int)sc.width - 1);
+    const int yr0 = max(y0 - fph, 0), yr1 = min(y0 + 8 + fph, (int)sc.height - 1);
     const float img_x = sx - 0.5f, img_y = sy - 0.5f;
-    const int bx = (int)floorf(img_x), by = (int)floorf(img_y);
-    const int ix_lo = max(0, bx - fpw), ix_hi = min((int)sc.width - 1, bx + fpw + 1);
-    const int iy_lo = max(0, by - fph), iy_hi = min((int)sc.height - 1, by + fph + 1);
+    int ix_lo, ix_hi, iy_lo, iy_hi;
+    film_admit(sx, xr0, xr1, fpw, ix_lo, ix_hi);
+    film_admit(sy, yr0, yr1, fph, iy_lo, iy_hi);
     for (int iy = iy_lo; iy <= iy_hi; ++iy) {
         const float fy = fabsf((float)iy - img_y) * sc.inv_h;
         if (fy > sc.filter_h) continue;
@@ -659,7 +679,7 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES_SIDE) void k_sampler_pass(co
         const uint32_t n_pairs = per_sub * per_tile;
         bool pairs_left = true, pending = false;
         float sx = 0.0f, sy = 0.0f;
-        uint32_t slot = 0u, i_smp = 0u;
+        uint32_t slot = 0u, i_smp = 0u, tile_smp = 0u;   // (tile_smp: the sample's tile in s_tiles)
         Lane ln;
         ln.flags = 0u;
         ln.illum = mk(0.0f, 0.0f, 0.0f);
@@ -668,7 +688,8 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES_SIDE) void k_sampler_pass(co
             const bool idle = !(ln.flags & LF_ALIVE);
             if (idle && pending) {   // the lane's previous sample is finished: RenderTarget::write it into the group's window, its luminance into the pixel's list
                 const f3 c = lane_result(ln);
-                film_splat_window(sc, s_win, wx0, wy0, ww, sc.filter_table, sx, sy, c);
+                const uint2 tile = s_tiles[tile_smp];
+                film_splat_window(sc, s_win, wx0, wy0, ww, sc.filter_table, (int)tile.x * 8, (int)tile.y * 8, sx, sy, c);
                 if (sp.kind == TRAY_SAMPLER_ADAPTIVE) px_lum[(size_t)slot * sp.lum_cap + sp.before + i_smp] = 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z;   // Colorf::luminance (color.rs:43-45)
                 pending = false;
             }
@@ -685,6 +706,7 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES_SIDE) void k_sampler_pass(co
                     const uint32_t t_in = pair / per_tile, rem = pair - t_in * per_tile, pix = rem / sp.count, i = rem - pix * sp.count;
                     const uint2 tile = s_tiles[first + t_in];
                     slot = (g0 + first + t_in) * 64u + pix;   // the pixel's index in the batch (px_state / px_lum)
+                    tile_smp = first + t_in;
                     if (!(sp.kind == TRAY_SAMPLER_ADAPTIVE && (px_state[slot] & 1u))) {   // (a pixel k_sampler_decide has finished sits out: its pairs are dropped)
                         const uint32_t px = tile.x * 8u + (pix & 7u), py = tile.y * 8u + (pix >> 3);
                         const uint32_t kp = key_pixel(kf, py * sc.width + px);

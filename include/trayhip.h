@@ -340,6 +340,17 @@ int tray_render_tiles_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t t
 int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles,
                              uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream);
 
+/* The samples [sample_begin, sample_end) of every pixel of tiles [tile_start, tile_start+tile_count) of a spp-sample
+ * LowDiscrepancy frame, added into rgbw_dev. Ranges that partition [0, spp) add up to tray_render_tiles_device's film. */
+/* Sample s of a pixel is the sample the whole frame traces at s (ld.rs:33-52 draws sample_02(i) / van_der_corput(i) of the frame's
+ * spp-long sequences; TRAY-CBRNG keys the rest by (seed, frame, pixel, s)), so a range is a progressive pass or a GPU's share of the
+ * samples, and the films of ranges are merged by addition (film/image.rs:21-50). tile_count == 0 selects the whole queue, as in
+ * tray_render_tiles_device; [0, spp) is that call. TrayKernelTiming counts the range's samples only. Returns TRAY_E_INVALID unless
+ * sample_begin < sample_end <= spp and spp is a power of two, TRAY_E_UNSUPPORTED while tray_scene_set_sampler has chosen Uniform or
+ * Adaptive (an Adaptive pass depends on the samples taken before it). */
+int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp,
+                               uint32_t sample_begin, uint32_t sample_end, uint64_t seed, float* rgbw_dev, void* stream);
+
 /* Host-side enumeration of the Morton-queue indices tray_render_shard_device renders for `shard`
  * (same mapping; lets callers and tests reason about the partition without a GPU). */
 int tray_shard_tiles(uint32_t n_tiles, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles,
@@ -442,6 +453,17 @@ int tray_debug_transform_table(TrayDeviceScene* s, uint32_t n, uint32_t* n_diffe
 typedef struct TrayMultiScene TrayMultiScene;
 int tray_multi_create(const TrayFlatScene* f, int n_dev, const int* dev_ids, TrayMultiScene** out);
 int tray_render_frame_multi(TrayMultiScene* m, uint32_t spp, uint64_t seed, float* rgbw_host);
+/* How tray_render_frame_multi splits a frame. TRAY_PARTITION_TILES (the default): device d renders shard d of the tiles (above).
+ * TRAY_PARTITION_SAMPLES: every device renders every tile, device d the samples tray_multi_shard_samples gives it
+ * (tray_render_samples_device) -- the same work per device by construction, where the reference deals blocks (exec/distrib/master.rs:91-93);
+ * the films are summed by the same one ncclReduce (film/image.rs:21-50). A device whose range is empty (n_dev > spp) launches nothing and
+ * joins the reduce. The render returns TRAY_E_UNSUPPORTED under TRAY_PARTITION_SAMPLES unless every device uses LowDiscrepancy (sampler/ld.rs).
+ * TRAY_E_INVALID for an unknown partition. */
+enum { TRAY_PARTITION_TILES = 0, TRAY_PARTITION_SAMPLES = 1 };
+int tray_multi_set_partition(TrayMultiScene* m, int partition);          /* default TILES: today's behaviour */
+/* host enumeration of device d's range under TRAY_PARTITION_SAMPLES: [floor(d*spp/n), floor((d+1)*spp/n)); TRAY_E_INVALID unless spp is a
+ * power of two and d < n_dev */
+int tray_multi_shard_samples(uint32_t spp, uint32_t d, uint32_t n_dev, uint32_t* begin, uint32_t* end);
 /* tray_scene_set_sampler on every device of m */
 int tray_multi_set_sampler(TrayMultiScene* m, uint32_t kind, uint32_t min_spp, uint32_t max_spp);
 /* tray_scene_set_wavefront on every device of m */

@@ -207,6 +207,9 @@ class Scene:
             pass
 
 
+_PARTITIONS = {"tiles": _lib.TRAY_PARTITION_TILES, "samples": _lib.TRAY_PARTITION_SAMPLES}   # tray_multi_set_partition
+
+
 class Hip:
     """Execution backend in the place of exec::MultiThreaded (src/exec/multithreaded.rs:20-70): renders
     config.select_blocks of frame config.current_frame on one MI355X and adds the result into rt."""
@@ -248,6 +251,40 @@ class Hip:
                                              C.c_void_p(int(rgbw_ptr)), C.c_void_p(int(stream)) if stream else None))
         return dev
 
+    def render_samples_device(self, scene, frame, select_blocks, spp, sample_range, rgbw_ptr, stream=None):
+        """Asynchronous: the samples [begin, end) = sample_range of every pixel of select_blocks of the spp-sample LowDiscrepancy frame,
+        accumulated into a device RGBW buffer (tray_render_samples_device). Ranges that partition [0, spp) add up to render_device's film."""
+        dev = scene.device_scene(frame, self.device)
+        spp = self._select_sampler(dev, spp)
+        begin, end = (int(v) for v in sample_range)
+        check(lib().tray_render_samples_device(dev, int(select_blocks[0]), int(select_blocks[1]), int(spp), begin, end, self.seed,
+                                               C.c_void_p(int(rgbw_ptr)), C.c_void_p(int(stream)) if stream else None))
+        return dev
+
+    def render_progressive(self, scene, rt, config, passes):
+        """Generator: config.select_blocks of the frame in `passes` consecutive sample ranges of nearly equal size ([k spp / passes,
+        (k + 1) spp / passes), at most spp of them), each added into rt as it is done; yields (samples_done, rt) after every pass. After the
+        last one rt holds what render() adds. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        import torch
+        if int(passes) < 1:
+            raise ValueError("render_progressive: passes must be >= 1")
+        dev = scene.device_scene(config.current_frame, self.device)
+        spp = self._select_sampler(dev, config.spp)
+        passes = min(int(passes), spp)
+        w, h = rt.dimensions()
+        with torch.cuda.device(self.device):
+            film = torch.empty(h * w * 4, dtype=torch.float32, device=f"cuda:{self.device}")
+            stream = torch.cuda.current_stream().cuda_stream
+            for k in range(passes):
+                begin, end = k * spp // passes, (k + 1) * spp // passes
+                film.zero_()
+                self.render_samples_device(scene, config.current_frame, config.select_blocks, spp, (begin, end), film.data_ptr(), stream or None)
+                rt.add_pixels(film.cpu().numpy())
+                t = _lib.TrayKernelTiming()
+                if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
+                    self.last_timing = t
+                yield end, rt
+
     def render_shard_device(self, scene, frame, shard, n_shards, spp, rgbw_ptr, chunk_tiles=16, stream=None):
         """One rank's share of a frame (round-robin chunks of the Morton queue); merge = sum over ranks."""
         dev = scene.device_scene(frame, self.device)
@@ -256,8 +293,10 @@ class Hip:
                                              C.c_void_p(int(rgbw_ptr)), C.c_void_p(int(stream)) if stream else None))
         return dev
 
-    def render_multi(self, scene, rt, config, devices):
-        """One frame on several GPUs of this process: tiles sharded round-robin over `devices`, the per-device films summed onto
+    def render_multi(self, scene, rt, config, devices, partition="tiles"):
+        """One frame on several GPUs of this process: tiles sharded round-robin over `devices` (partition="tiles"), or every tile on every
+        device with device d rendering the samples multi.shard_samples(spp, d, len(devices)) gives it (partition="samples": equal work per
+        device; LowDiscrepancy only), the per-device films summed onto
         the first one by RCCL inside the library (tray_render_frame_multi; the master's Image::add_blocks merge,
         exec/distrib/master.rs:124-163, film/image.rs:36-50), the result added into rt. Returns (per-device timings, reduce ms).
         The per-device scenes and the communicators are kept between calls: another frame of the same scene on the same devices
@@ -282,6 +321,9 @@ class Hip:
                 raise
             self._multi_frame = config.current_frame
         spp = self._select_sampler(self._multi, config.spp, multi=True)
+        if partition not in _PARTITIONS:
+            raise ValueError(f"render_multi: partition must be one of {sorted(_PARTITIONS)}")
+        check(lib().tray_multi_set_partition(self._multi, _PARTITIONS[partition]))
         check(lib().tray_render_frame_multi(self._multi, spp, self.seed, rt.pixels.ctypes.data))
         per = (_lib.TrayKernelTiming * len(devices))()
         ms = C.c_float()

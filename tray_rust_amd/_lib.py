@@ -12,6 +12,7 @@ GEOM_SPHERE, GEOM_DISK, GEOM_RECT, GEOM_MESH, GEOM_NONE = 0, 1, 2, 3, 4
 INST_RECEIVER, INST_AREA_EMITTER, INST_POINT_EMITTER = 0, 1, 2
 MAT_MATTE, MAT_PLASTIC, MAT_METAL, MAT_GLASS, MAT_ROUGH_GLASS, MAT_SPECULAR_METAL, MAT_MERL = range(7)
 FILTER_TABLE_SIZE = 16
+TRAY_PARTITION_TILES, TRAY_PARTITION_SAMPLES = 0, 1
 
 
 class TrayError(RuntimeError):
@@ -177,6 +178,9 @@ SYMBOLS = {
     "tray_adaptive_step": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "tray_render_tiles_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "tray_render_shard_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "tray_render_samples_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "tray_multi_set_partition": (C.c_int, [C.c_void_p, C.c_int]),
+    "tray_multi_shard_samples": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "tray_shard_tiles": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),
     "tray_multi_create": (C.c_int, [_P(TrayFlatScene), C.c_int, _P(C.c_int), _P(C.c_void_p)]),
     "tray_render_frame_multi": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]),

@@ -6,6 +6,7 @@
 #include <cmath>
 #define TR_INST_EXTERN   // explicit instantiation declarations of every kernel the launch sites below name
 #include "kernel_list.h"
+#include "kernel_ranges.h"
 #undef TR_INST_EXTERN
 
 
@@ -201,15 +202,17 @@ struct WfView {
 };
 template <int ANIM>
 static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride, uint32_t spp,
-                     uint32_t kf, float* rgbw_dev, uint32_t slice_shift) {
+                     uint32_t kf, float* rgbw_dev, uint32_t slice_shift, uint32_t smp_begin, uint32_t smp_end) {
     const WfBuffers& w = s->lb.wf;
     const dim3 grid(v.n_chunks), block(TR_BLOCK);
     const dim3 qgrid((v.n_chunks + WF_SEGS - 1u) / WF_SEGS * WF_SEGS);   // one-thread-per-entry kernels: block b reads segment b % WF_SEGS
     const dim3 tgrid(std::min<uint32_t>(w.n_blocks_trace, v.n_chunks));
     const uint32_t n_active = v.n_chunks * TR_BLOCK;
     hipStream_t stream = v.stream;
-    hipLaunchKernelGGL(k_wf_advance<ANIM>, grid, block, 0, stream, v.dev, v.pool, v.chunks, v.bins, tiles, tile_count, chunk, chunk_stride,
-                       spp, kf, rgbw_dev, w.d_wf_counters, w.d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift);
+    if (smp_end) tr_ranges::wf_advance(ANIM, grid, block, stream, v.dev, v.pool, v.chunks, v.bins, tiles, tile_count, chunk, chunk_stride,   // (a sample range)
+                                       spp, kf, rgbw_dev, w.d_wf_counters, w.d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift, smp_begin, smp_end);
+    else hipLaunchKernelGGL(k_wf_advance<ANIM>, grid, block, 0, stream, v.dev, v.pool, v.chunks, v.bins, tiles, tile_count, chunk, chunk_stride,
+                            spp, kf, rgbw_dev, w.d_wf_counters, w.d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift);
     hipLaunchKernelGGL(k_wf_regen<ANIM>, qgrid, block, 0, stream, v.dev, v.pool, v.chunks, tiles, chunk, chunk_stride, spp, kf, s->d_stats, v.qr, v.qa, v.qctl, slice_shift);
     // (each traversal is followed by the few-thread kernel that traces the rays it handed over to the reference's binary traversal:
     // direction components that are zero / denormal / not finite -- normally none, the kernel reads one word and exits. The deferred rays'
@@ -867,8 +870,9 @@ int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* f) {
     return TRAY_OK;
 }
 
+// smp_begin / smp_end: the sample range [smp_begin, smp_end) of the spp-sample LowDiscrepancy frame to render (tray_render_samples_device); 0 / 0 = all of [0, spp)
 static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
-                        uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_);
+                        uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_, uint32_t smp_begin = 0u, uint32_t smp_end = 0u);
 
 // every buffer of the wavefront schedule for a pool of n_slots; on failure nothing stays allocated and TRAY_E_NOMEM is returned
 static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
@@ -943,15 +947,16 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
 // Wavefront schedule: rounds of six stage kernels over the path pool until every tile is done.
 // The host only polls a "tiles done" word every WF_POLL rounds; kernels of finished chunks exit at once.
 static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
-                            uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream) {
+                            uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     const WfBuffers& w = s->lb.wf;
+    const uint32_t n = smp_end ? smp_end - smp_begin : spp;   // samples per pixel this launch renders: the rules below cut them (a slice is never empty: 2^slice_shift <= n)
     // tiles are cut into slices of their samples while the pool has at least as many chunks as the launch then has work items
     // (k_wf_advance; a slice costs its own film resolve: at 8 M slots and 32 400 tiles halving them measured 124 against 132 Msamples/s); a
     // slice keeps at least 16 samples per pixel (TRAYHIP_WF_SLICES overrides: 1, 2, 4)
     uint32_t slice_shift = 0u;
-    while ((1u << (slice_shift + 1u)) <= WF_MAX_SLICES && ((uint64_t)tile_count << (slice_shift + 1u)) <= w.n_chunks && (spp >> (slice_shift + 1u)) >= 16u) ++slice_shift;   // (cut while the items still fit the chunks: one item per chunk is the optimum)
-    if (s->wf_req_slices) { slice_shift = 0u; while ((2u << slice_shift) <= s->wf_req_slices && (2u << slice_shift) <= WF_MAX_SLICES && (spp >> (slice_shift + 1u)) >= 1u) ++slice_shift; }   // tray_scene_set_wavefront
-    if (const char* e = getenv("TRAYHIP_WF_SLICES")) { slice_shift = 0u; while ((2u << slice_shift) <= (uint32_t)std::max(1, atoi(e)) && (2u << slice_shift) <= WF_MAX_SLICES && (spp >> (slice_shift + 1u)) >= 1u) ++slice_shift; }
+    while ((1u << (slice_shift + 1u)) <= WF_MAX_SLICES && ((uint64_t)tile_count << (slice_shift + 1u)) <= w.n_chunks && (n >> (slice_shift + 1u)) >= 16u) ++slice_shift;   // (cut while the items still fit the chunks: one item per chunk is the optimum)
+    if (s->wf_req_slices) { slice_shift = 0u; while ((2u << slice_shift) <= s->wf_req_slices && (2u << slice_shift) <= WF_MAX_SLICES && (n >> (slice_shift + 1u)) >= 1u) ++slice_shift; }   // tray_scene_set_wavefront
+    if (const char* e = getenv("TRAYHIP_WF_SLICES")) { slice_shift = 0u; while ((2u << slice_shift) <= (uint32_t)std::max(1, atoi(e)) && (2u << slice_shift) <= WF_MAX_SLICES && (n >> (slice_shift + 1u)) >= 1u) ++slice_shift; }
     tile_count <<= slice_shift;   // from here on: work items
     const uint32_t n_chunks = std::min(w.n_chunks, tile_count);
     HIP_CHECK(hipMemsetAsync(w.d_wf_counters, 0, 2 * sizeof(uint32_t), stream));
@@ -1010,15 +1015,15 @@ static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t ti
     }
     // every chunk needs at most (spp/4 rounded up) samples x (max_depth + 2) rounds per tile, plus one round per tile switch
     const uint64_t tiles_per_chunk = (tile_count + n_chunks - 1) / n_chunks;
-    const uint64_t max_rounds = tiles_per_chunk * (((uint64_t)(spp >> slice_shift) + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * s->dev.max_depth + 3) + 4) + 2 * WF_POLL;   // (WF_FOLD_C: a vertex with a stage C ray takes two rounds)
+    const uint64_t max_rounds = tiles_per_chunk * (((uint64_t)((n + (1u << slice_shift) - 1u) >> slice_shift) + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * s->dev.max_depth + 3) + 4) + 2 * WF_POLL;   // (WF_FOLD_C: a vertex with a stage C ray takes two rounds)
     bool done = false;
     for (uint32_t k = 0; k < n_views; ++k) HIP_CHECK(hipMemsetAsync(views[k].qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t), views[k].stream));   // (later: inside wf_round)
     for (uint32_t round = 0; !done; ++round) {
         for (uint32_t k = 0; k < n_views; ++k) {
             const WfView& v = views[k];
             if (v.bin_ctl && s->wf_bin_stages) HIP_CHECK(hipMemsetAsync(v.bin_ctl, 0, (size_t)2u * 2u * WF_SEGS * WF_BINS * sizeof(uint32_t), v.stream));
-            if (s->animated) wf_round<1>(s, v, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift);
-            else wf_round<0>(s, v, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift);
+            if (s->animated) wf_round<1>(s, v, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift, smp_begin, smp_end);
+            else wf_round<0>(s, v, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift, smp_begin, smp_end);
             launches += (WF_FOLD_C ? 8 : 10) + ((s->wf_bin_stages & 1u) ? 2 : 0) + ((s->wf_bin_stages & 2u) ? 2 : 0);   // (nominal: a kind-pure launch per material kind present comes on top in both forms)
         }
         if (round % WF_POLL == WF_POLL - 1) {
@@ -1077,10 +1082,31 @@ int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shar
     return launch_tiles(s, shard * chunk_tiles, work, chunk_tiles, n_shards, spp, seed, rgbw_dev, stream_);
 }
 
+int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint32_t sample_begin, uint32_t sample_end,
+                               uint64_t seed, float* rgbw_dev, void* stream_) {
+    if (!s || !rgbw_dev) { set_error("tray_render_samples_device: null argument"); return TRAY_E_INVALID; }
+    if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID; }
+    if (sample_begin >= sample_end || sample_end > spp) { set_error("tray_render_samples_device: the range must satisfy sample_begin < sample_end <= spp"); return TRAY_E_INVALID; }
+    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error("tray_render_samples_device: sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
+    if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // as tray_render_tiles_device
+    if (tile_start > s->n_tiles) tile_start = s->n_tiles;
+    if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
+    return launch_tiles(s, tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
+}
+
+int tray_multi_shard_samples(uint32_t spp, uint32_t d, uint32_t n_dev, uint32_t* begin, uint32_t* end) {
+    if (!begin || !end) { set_error("tray_multi_shard_samples: null argument"); return TRAY_E_INVALID; }
+    if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID; }
+    if (n_dev == 0 || d >= n_dev) { set_error("tray_multi_shard_samples: device index out of range"); return TRAY_E_INVALID; }
+    *begin = (uint32_t)((uint64_t)d * spp / n_dev);
+    *end = (uint32_t)((uint64_t)(d + 1u) * spp / n_dev);
+    return TRAY_OK;
+}
+
 // thread_work with sampler::Uniform / sampler::Adaptive (include/trayhip.h: tray_scene_set_sampler): rounds of k_sampler_pass (+
 // k_sampler_decide) over batches of tiles, all on `stream`, no host synchronisation -- a pixel that is finished sits out the later rounds.
 static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
-                          uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream) {
+                          uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     SamplerPass sp{};
     sp.kind = s->sampler_kind; sp.min_spp = s->smp_min; sp.max_spp = s->smp_max;
     uint32_t rounds = 1;
@@ -1113,6 +1139,7 @@ static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile
         for (uint32_t j = 0; j < rounds; ++j) {
             sp.pass = j;
             sp.count = sp.kind == TRAY_SAMPLER_ADAPTIVE ? (j == 0u ? sp.min_spp : sp.step) : sp.min_spp;   // (Uniform: 1, LowDiscrepancy: spp)
+            if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY && smp_end) sp.count = smp_end - smp_begin;   // (a range: its samples of the spp-sample frame, from smp_begin on)
             sp.taken = sp.kind == TRAY_SAMPLER_ADAPTIVE ? sp.min_spp + j * sp.step : 0u;
             sp.before = j == 0u ? 0u : sp.min_spp + (j - 1u) * sp.step;
             // (k_sampler_pass: a workgroup owns a group of consecutive tiles -- enough of them for ~4096 (pixel, sample) pairs of the round, 16 at most: a
@@ -1123,7 +1150,10 @@ static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile
             const dim3 grid((n_items + group - 1u) / group), block(TR_BLOCK);
 #define SAMPLER_PASS(A, F) hipLaunchKernelGGL((k_sampler_pass<A, F>), grid, block, s->stack_bytes, stream, s->dev, s->d_tiles + tile_start, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group)
             const bool lean = s->feat == FEAT_NONE && s->dev.integrator != TRAY_INTEGRATOR_WHITTED;   // (no optional lobe, no texture: the small instantiation)
-            if (s->deforming) { if (lean) SAMPLER_PASS(3, FEAT_NONE); else SAMPLER_PASS(3, FEAT_ALL | FEAT_TEX); }
+            if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY && smp_end)
+                tr_ranges::sampler_pass(s->deforming ? 3 : s->animated ? 2 : 0, lean, grid, block, s->stack_bytes, stream, s->dev, s->d_tiles + tile_start, item0, n_items, chunk,
+                                        chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group, smp_begin);
+            else if (s->deforming) { if (lean) SAMPLER_PASS(3, FEAT_NONE); else SAMPLER_PASS(3, FEAT_ALL | FEAT_TEX); }
             else if (s->animated) { if (lean) SAMPLER_PASS(2, FEAT_NONE); else SAMPLER_PASS(2, FEAT_ALL | FEAT_TEX); }
             else { if (lean) SAMPLER_PASS(0, FEAT_NONE); else SAMPLER_PASS(0, FEAT_ALL | FEAT_TEX); }
 #undef SAMPLER_PASS
@@ -1263,7 +1293,7 @@ static int launch_prepare(TrayDeviceScene* s, uint64_t samples, hipStream_t stre
 }
 
 static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
-                        uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_) {
+                        uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_, uint32_t smp_begin, uint32_t smp_end) {
     if (s->sampler_kind == TRAY_SAMPLER_LOW_DISCREPANCY && (spp == 0 || (spp & (spp - 1)) != 0)) {
         set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID;
     }
@@ -1283,12 +1313,14 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     uint32_t kf = mix((uint32_t)seed + 0x9E3779B9u);
     kf = mix(kf ^ (uint32_t)(seed >> 32));
     kf = mix(kf + s->dev.frame);
-    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream);
+    if (smp_begin == 0u && smp_end == spp) smp_end = 0u;   // (the whole frame as a range: the whole-frame launch)
+    const uint32_t n_smp = smp_end ? smp_end - smp_begin : spp;   // samples per pixel of this launch
+    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
     s->last_was_wavefront = false;
     const bool had_pool = s->lb.wf.ready;
     {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = launch_prepare(s, (uint64_t)tile_count * 64u * spp, stream);
+        const int rc = launch_prepare(s, (uint64_t)tile_count * 64u * n_smp, stream);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] launch buffers prepared in %.1f ms (table %s, %u of %u records per index in use; pool %s: %u slots)\n",
                                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), s->lb.last_used_table ? "on" : "off",
                                              s->lb.xf_table_stride, s->lb.xf_table_cap, had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
@@ -1296,7 +1328,7 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     }
     if (s->wavefront) {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = launch_wavefront(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream);
+        const int rc = launch_wavefront(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] wavefront launch enqueued in %.1f ms (pool %s: %u slots)\n",
                                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
         return rc;
@@ -1307,16 +1339,16 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     // round of the 768 workgroups is one such tile), the whole cornell_box frame 1160.9 / 1163.5 / 1163.6 / 1159.9 / 1154.3; a GPU's eighth of the
     // frame (4050 tiles, slowest of the eight shards against an eighth of the whole frame): dragon 0.449 / 0.632 / 0.784 / 0.862 / 0.872,
     // cornell_box 0.895 / 0.942 / 0.960 / 0.971 / 0.975. So: three items per tile for a launch with many tiles per workgroup, up to five for a small one.
-    // TRAYHIP_TILE_SLICES=<items per tile> overrides.
+    // TRAYHIP_TILE_SLICES=<items per tile> overrides. A sample range is cut by the same rules over its n_smp samples (k_path_tiles: any n_smp >= 1).
     uint32_t levels = 1u;
     {
         // (a launch with many tiles per workgroup keeps >= 256 samples per slice: at 256 spp three items per tile cost cornell_box 2.8 %, 1114 against 1146
         // Msamples/s, profiles/r06_c2_kept_gate_distance_ab.txt -- the resolves outweigh a tail that is 1 / 42 of the launch there)
         const bool small = tile_count < 12u * (uint32_t)s->n_blocks;
         const uint32_t most = small ? 5u : 3u, least = small ? 64u : 256u;
-        while (levels < most && (spp >> levels) >= least) ++levels;   // (the last two slices are spp >> (levels - 1) samples each)
+        while (levels < most && (n_smp >> levels) >= least) ++levels;   // (the last two slices are spp >> (levels - 1) samples each)
     }
-    if (const char* e = getenv("TRAYHIP_TILE_SLICES")) { levels = 1u; const uint32_t want = (uint32_t)std::max(1, atoi(e)); while (levels < want && (spp >> levels) >= 1u) ++levels; }
+    if (const char* e = getenv("TRAYHIP_TILE_SLICES")) { levels = 1u; const uint32_t want = (uint32_t)std::max(1, atoi(e)); while (levels < want && (n_smp >> levels) >= 1u) ++levels; }
     int blocks = (int)std::min<uint64_t>((uint64_t)s->n_blocks, (uint64_t)tile_count * levels);
 #ifdef TR_SAMPLE_DUMP
     void* dump_buf = nullptr;
@@ -1336,7 +1368,9 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
                              else if (s->feat == (FEAT_ALL | FEAT_TEX)) PATH_TILES(A, FEAT_ALL | FEAT_TEX); else PATH_TILES(A, FEAT_ALL); } while (0)
 #define WHITTED_TILES(A) hipLaunchKernelGGL((k_path_tiles<A, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>), dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, \
                                              s->d_tiles + tile_start, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats)
-    if (s->dev.integrator == TRAY_INTEGRATOR_WHITTED) { if (s->animated) WHITTED_TILES(1); else WHITTED_TILES(0); }
+    if (smp_end) tr_ranges::path_tiles(s->animated ? 1 : 0, s->feat, s->dev.integrator == TRAY_INTEGRATOR_WHITTED, s->light_filter, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream,
+                                       s->launch_dev, s->d_tiles + tile_start, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats, smp_begin, smp_end);
+    else if (s->dev.integrator == TRAY_INTEGRATOR_WHITTED) { if (s->animated) WHITTED_TILES(1); else WHITTED_TILES(0); }
     else if (s->animated) PATH_TILES_F(1);
     else PATH_TILES_F(0);
 #undef WHITTED_TILES
@@ -1426,6 +1460,7 @@ struct TrayMultiScene {
     std::vector<hipStream_t> streams;
     std::vector<void*> comms;           // ncclComm_t
     size_t n_floats = 0;
+    int partition = TRAY_PARTITION_TILES;   // tray_multi_set_partition
     float reduce_ms = 0.0f;
     hipEvent_t r0 = nullptr, r1 = nullptr;   // around the reduce, on the first device's stream
 };
@@ -1502,6 +1537,13 @@ int tray_multi_set_sampler(TrayMultiScene* m, uint32_t kind, uint32_t min_spp, u
     return TRAY_OK;
 }
 
+int tray_multi_set_partition(TrayMultiScene* m, int partition) {
+    if (!m) { set_error("tray_multi_set_partition: null argument"); return TRAY_E_INVALID; }
+    if (partition != TRAY_PARTITION_TILES && partition != TRAY_PARTITION_SAMPLES) { set_error("tray_multi_set_partition: unknown partition " + std::to_string(partition)); return TRAY_E_INVALID; }
+    m->partition = partition;
+    return TRAY_OK;
+}
+
 int tray_multi_update_frame(TrayMultiScene* m, const TrayFlatScene* f) {
     if (!m || !f) { set_error("tray_multi_update_frame: null argument"); return TRAY_E_INVALID; }
     int current = 0;
@@ -1521,6 +1563,12 @@ struct CurrentDeviceGuard {   // the multi-device entry points leave the caller'
 
 int tray_render_frame_multi(TrayMultiScene* m, uint32_t spp, uint64_t seed, float* rgbw_host) {
     if (!m || !rgbw_host) { set_error("tray_render_frame_multi: null argument"); return TRAY_E_INVALID; }
+    const bool by_samples = m->partition == TRAY_PARTITION_SAMPLES;
+    if (by_samples) {   // (refused before any device starts: a range of Uniform / Adaptive has no meaning)
+        if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID; }
+        for (TrayDeviceScene* s : m->scenes)
+            if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error("tray_render_frame_multi: the samples partition needs the LowDiscrepancy sampler"); return TRAY_E_UNSUPPORTED; }
+    }
     CurrentDeviceGuard keep_current;
     // one host thread per device: the wavefront schedule polls its stream, and the launches of different devices must overlap
     std::vector<int> rcs(m->n_dev, TRAY_OK);
@@ -1531,7 +1579,14 @@ int tray_render_frame_multi(TrayMultiScene* m, uint32_t spp, uint64_t seed, floa
             if (hipSetDevice(m->dev_ids[d]) != hipSuccess || hipMemsetAsync(m->films[d], 0, m->n_floats * sizeof(float), m->streams[d]) != hipSuccess) {
                 rcs[d] = TRAY_E_DEVICE; errs[d] = "hipSetDevice / hipMemsetAsync failed"; return;
             }
-            rcs[d] = tray_render_shard_device(m->scenes[d], (uint32_t)d, (uint32_t)m->n_dev, 16u, spp, seed, m->films[d], m->streams[d]);
+            if (by_samples) {   // every tile, device d's range of the samples (exec/distrib/master.rs:91-93 deals blocks; the film is a sum either way)
+                uint32_t b = 0u, e = 0u;
+                (void)tray_multi_shard_samples(spp, (uint32_t)d, (uint32_t)m->n_dev, &b, &e);
+                rcs[d] = b < e ? tray_render_samples_device(m->scenes[d], 0u, 0u, spp, b, e, seed, m->films[d], m->streams[d])
+                               : launch_tiles(m->scenes[d], 0, 0, 1, 1, spp, seed, m->films[d], m->streams[d]);   // (an empty range: no launch, the film joins the reduce as zeros)
+            } else {
+                rcs[d] = tray_render_shard_device(m->scenes[d], (uint32_t)d, (uint32_t)m->n_dev, 16u, spp, seed, m->films[d], m->streams[d]);
+            }
             if (rcs[d] != TRAY_OK) errs[d] = tray_last_error();
         });
     for (std::thread& w : workers) w.join();

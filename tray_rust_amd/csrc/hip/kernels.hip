@@ -240,7 +240,11 @@ template <int ANIM, int FEAT, int INTEG = TRAY_INTEGRATOR_PATH, bool LFILT = fal
 __global__ __launch_bounds__(TR_BLOCK, (FEAT == 15 || INTEG != TRAY_INTEGRATOR_PATH) ? TR_MIN_WAVES_SIDE : ANIM ? TR_MIN_WAVES_ANIM : TR_MIN_WAVES) void k_path_tiles(const DevScene scv, const uint2* __restrict__ tiles, uint32_t tile_count,
                                                          uint32_t chunk, uint32_t chunk_stride, uint32_t spp, uint32_t kf, uint32_t levels,
                                                          float* __restrict__ rgbw, uint32_t* __restrict__ counter,
-                                                         DevStats* __restrict__ stats) {
+                                                         DevStats* __restrict__ stats
+#ifdef TR_SAMPLE_RANGES   // the sample-range instantiations (kernel_ranges.hip, libtrayhip_ranges.so): [smp_begin, smp_end) of the frame, 0 / 0 = all of it
+                                                         , uint32_t smp_begin = 0u, uint32_t smp_end = 0u
+#endif
+                                                         ) {
     const float* __restrict__ const s_table = sc_filter_table(scv);   // the 16 x 16 table stays in global memory (1 KB, cache resident): with the row-binned film only
                                                                        // the ~1 in 1000 samples on a class boundary read it, and the kilobyte decides whether a
                                                                        // third workgroup fits the CU's LDS on mesh scenes (42 granules of 1280 B per workgroup)
@@ -283,10 +287,18 @@ __global__ __launch_bounds__(TR_BLOCK, (FEAT == 15 || INTEG != TRAY_INTEGRATOR_P
         // workgroups is 1 / 2^(L-1) of a tile instead of a whole one. That is what a GPU's share of a frame needs when tiles differ in cost: one
         // eighth of the dragon frame ran at 0.70 of the whole frame's rate with two equal slices per tile, because a workgroup that drew a
         // mesh tile last kept the launch alive for half a heavy tile (profiles/r06_eighth_rate_all_shards.txt). L = 1: whole tiles.
+        // A sample RANGE [smp_begin, smp_end) of the spp-sample frame (TR_SAMPLE_RANGES builds, tray_render_samples_device) is sliced the same way over
+        // its n samples: level l is [n - (n >> l), n - (n >> (l + 1))), the last level [n - (n >> last), n), shifted by smp_begin. For a power of two
+        // these are the slices above; for any n they partition [0, n), and the host's rule keeps n >> last >= 1, so no slice is empty.
         const uint32_t item = s_tile;
         if (item >= tile_count * levels) break;
         const uint32_t level = item / tile_count, ti = item - level * tile_count, last = levels - 1u;
+#ifdef TR_SAMPLE_RANGES
+        const uint32_t n_smp = smp_end ? smp_end - smp_begin : spp;
+        const uint32_t s_lo = smp_begin + n_smp - (n_smp >> level), s_per_slice = (level < last ? n_smp - (n_smp >> (level + 1u)) : n_smp) - (n_smp - (n_smp >> level));
+#else
         const uint32_t s_per_slice = level < last ? spp >> (level + 1u) : spp >> last, s_lo = level < last ? spp - (spp >> level) : spp - (spp >> last);
+#endif
         const uint2 tile = tiles[(ti / chunk) * chunk_stride * chunk + (ti % chunk)];
         const int x0 = (int)tile.x * 8, y0 = (int)tile.y * 8;
         // The (pixel, sample) pairs of the slice are handed out dynamically: a lane whose path ended takes the next pair of the
@@ -637,7 +649,11 @@ template <int ANIM, int FEAT = FEAT_ALL | FEAT_TEX>
 __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES_SIDE) void k_sampler_pass(const DevScene scv, const uint2* __restrict__ tiles, uint32_t item0, uint32_t n_items,
                                                            uint32_t chunk, uint32_t chunk_stride, uint32_t kf, SamplerPass sp,
                                                            const uint32_t* __restrict__ px_state, float* __restrict__ px_lum,
-                                                           float* __restrict__ rgbw, DevStats* __restrict__ stats, uint32_t group) {
+                                                           float* __restrict__ rgbw, DevStats* __restrict__ stats, uint32_t group
+#ifdef TR_SAMPLE_RANGES   // LowDiscrepancy over a sample range (kernel_ranges.hip): sample smp_first + i of the frame's sp.max_spp = spp, sp.count = the range's samples
+                                                           , uint32_t smp_first = 0u
+#endif
+                                                           ) {
     TR_DYN_LDS(uint32_t, s_stack);
     __shared__ float s_win[4 * SP_WIN_MAX * SP_WIN_MAX];
     __shared__ uint2 s_tiles[SP_GROUP_MAX];
@@ -713,8 +729,13 @@ __global__ __launch_bounds__(TR_BLOCK, TR_MIN_WAVES_SIDE) void k_sampler_pass(co
                         float t;
                         uint32_t ks;
                         if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY) {                          // the tile kernel's samples (scenes with an AnimatedMesh)
+#ifdef TR_SAMPLE_RANGES
+                            pixel_sample(kp, smp_first + i, sp.max_spp, px, py, sx, sy, t);   // (a range's samples are the frame's)
+                            ks = key_sample(kp, smp_first + i);
+#else
                             pixel_sample(kp, i, sp.count, px, py, sx, sy, t);
                             ks = key_sample(kp, i);
+#endif
                         } else if (sp.kind == TRAY_SAMPLER_UNIFORM) {
                             sx = (float)px + 0.5f; sy = (float)py + 0.5f;                      // uniform.rs:28
                             t = (float)(draw(kp, PD_SCR_T) >> 8) / 16777216.0f;                // uniform.rs:42-46

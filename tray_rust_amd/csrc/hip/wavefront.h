@@ -1221,12 +1221,23 @@ __global__ __launch_bounds__(TR_BLOCK) void k_wf_advance(const DevScene scv, WfP
                                                          float* __restrict__ rgbw, uint32_t* __restrict__ tile_counter,
                                                          uint32_t* __restrict__ tiles_done, DevStats* __restrict__ stats,
                                                          uint32_t* __restrict__ queue_a, uint32_t* __restrict__ queue_r,
-                                                         uint32_t* __restrict__ qctl, uint32_t slice_shift) {
+                                                         uint32_t* __restrict__ qctl, uint32_t slice_shift
+#ifdef TR_SAMPLE_RANGES   // the sample-range instantiations (kernel_ranges.hip): [smp_begin, smp_end) of the frame, 0 / 0 = all of it
+                                                         , uint32_t smp_begin = 0u, uint32_t smp_end = 0u
+#endif
+                                                         ) {
     // A work item is a SLICE of a tile: samples [slice, slice + 1) * (spp >> slice_shift) of its 64 pixels (item = tile << slice_shift | slice;
     // tile_count counts items). The film is a sum and every sample is keyed by pixel and index, so the slices of a tile are independent:
     // launch_wavefront cuts tiles when the pool has more chunks than the launch has tiles -- the schedule's rate grows with the slots in flight
     // (C5 stand-in 78 / 106 / 132 Msamples/s at 2 / 4 / 8 M slots), and one chunk per tile capped them at 4 per pixel.
+    // A sample range [smp_begin, smp_end) of the frame (0 / 0: all of [0, spp)) of n samples: slice j is smp_begin + [j n, (j + 1) n) >> slice_shift --
+    // the slices above when n = spp, equal to within one sample for any other n (the host keeps 2^slice_shift <= n, so none is empty).
+#ifdef TR_SAMPLE_RANGES
+    const uint32_t n_smp = smp_end ? smp_end - smp_begin : spp, slice_mask = (1u << slice_shift) - 1u;
+    const auto slice_lo = [&](uint32_t j) { return (uint32_t)(((uint64_t)j * n_smp) >> slice_shift); };
+#else
     const uint32_t s_per = spp >> slice_shift, n_pairs = 64u * s_per;
+#endif
     __shared__ float s_win[4 * WIN_PLANE];
     __shared__ float s_table[TRAY_FILTER_TABLE_SIZE * TRAY_FILTER_TABLE_SIZE];
     __shared__ float s_tx[TRAY_FILTER_TABLE_SIZE], s_ty[TRAY_FILTER_TABLE_SIZE];
@@ -1251,7 +1262,12 @@ __global__ __launch_bounds__(TR_BLOCK) void k_wf_advance(const DevScene scv, WfP
     bool closed_here = false;   // this kernel ran the slot's vertex_end (the vertex had a stage C ray): if the path goes on, its ray is queued here
     const bool film_rows = sc.film_rows != 0u;
     if (tile_idx != WF_TILE_NEED) {
+#ifdef TR_SAMPLE_RANGES
+        const uint32_t tile_of = tile_idx >> slice_shift, slice = tile_idx & slice_mask;
+        const uint32_t n_pairs = 64u * (slice_lo(slice + 1u) - slice_lo(slice));
+#else
         const uint32_t tile_of = tile_idx >> slice_shift;
+#endif
         const uint2 tile = tiles[(tile_of / chunk) * chunk_stride * chunk + (tile_of % chunk)];
         const int x0 = (int)tile.x * 8, y0 = (int)tile.y * 8;
         // ---- stage C shading of the previous round
@@ -1349,6 +1365,9 @@ __global__ __launch_bounds__(TR_BLOCK) void k_wf_advance(const DevScene scv, WfP
     // tile kernel: an idle slot takes the next pair of the chunk's counter whatever pixel it belongs to, so no slot sits out the end
     // of a tile because its own pixel's samples are used up while other pixels' are not.
     const bool idle = tile_idx != WF_TILE_IDLE && !(flags & LF_ALIVE);
+#ifdef TR_SAMPLE_RANGES
+    const uint32_t slice = tile_idx & slice_mask, s_lo = smp_begin + slice_lo(slice), n_pairs = 64u * (smp_begin + slice_lo(slice + 1u) - s_lo);   // (the chunk's item now)
+#endif
     bool wants_sample = false;
     {
         const unsigned long long im = __ballot(idle);
@@ -1359,7 +1378,11 @@ __global__ __launch_bounds__(TR_BLOCK) void k_wf_advance(const DevScene scv, WfP
             base = __shfl(base, (int)leader);
             const uint32_t pair = base + (uint32_t)__popcll(im & ((1ull << lane) - 1ull));
             // (stored with the slice's first sample in the sample bits: wf_regenerate and the film's row bins read pixel and sample from it)
+#ifdef TR_SAMPLE_RANGES
+            if (idle && pair < n_pairs) { pu(pool, F_SNEXT, i) = pair + (s_lo << 6); wants_sample = true; }
+#else
             if (idle && pair < n_pairs) { pu(pool, F_SNEXT, i) = pair + (((tile_idx & ((1u << slice_shift) - 1u)) * s_per) << 6); wants_sample = true; }
+#endif
         }
     }
     wf_enqueue(pool, queue_r, qctl, 6u, wants_sample, i);

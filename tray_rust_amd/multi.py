@@ -21,6 +21,15 @@ def shard_tiles(n_tiles, rank, world, chunk_tiles=DEFAULT_CHUNK_TILES):
     return list(buf[:n.value])
 
 
+def shard_samples(spp, rank, world):
+    """The sample range [begin, end) rank `rank` of `world` renders of every tile when a frame is split by samples (same mapping as
+    tray_multi_shard_samples: [floor(rank spp / world), floor((rank + 1) spp / world)), empty when world > spp); render it with
+    Hip.render_samples_device and merge the films with merge_film as for shard_tiles."""
+    b, e = C.c_uint32(), C.c_uint32()
+    check(lib().tray_multi_shard_samples(int(spp), int(rank), int(world), C.byref(b), C.byref(e)))
+    return b.value, e.value
+
+
 def merge_film(film, dst=0):
     """Sum the per-rank RGBW films into rank `dst` (film::Image::add_pixels semantics). No-op for one rank."""
     import torch.distributed as dist

@@ -7,12 +7,15 @@ With N GPUs the frame's tiles are sharded round-robin over the ranks (one proces
 per-rank RGBW buffers are merged with one RCCL sum-reduce to rank 0 inside the timed region
 (strong scaling of one frame, the reference's distributed mode: exec/distrib/master.rs:91-93).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` (HBM-bound
-accounting of SURVEY 8d: 368 B per path vertex + 16 B per pixel) and `cpu_baseline` (the C++
-oracle in faithful-transform mode on all host cores, bounded tile sample, N=1 only).
+Prints ONE JSON line on rank 0, with `roofline` (HBM-bound accounting of SURVEY 8d: 368 B per
+path vertex + 16 B per pixel, from the timed launches' HIP events and the committed counters).
+A plain run does only that: it sets up, warms up, times the steps, dumps and prints. --full
+adds what takes runs of its own (N=1 only): `workloads` (BASELINE.json configs[2..4], beside
+the default cornell_box line) and `cpu_baseline` (the C++ oracle in faithful-transform mode on
+all host cores, bounded tile sample).
 
 --dump-outputs DIR writes the RGBW film(s) the last timed step produced as DIR/*.npy (float32), so that two builds can be
 compared output for output: the inputs (seeded scenes, seed 1) are the same from run to run with the same arguments. The film
@@ -185,7 +188,7 @@ def pmc_views(workload, samples, kernel_seconds):
     return traffic, valu, compute
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2, help="timed steps of the reported workload (>= 1)")
@@ -193,8 +196,10 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the film(s) of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--spp", type=int, default=0, help="debug only: the reported config is 1024 spp")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="only the reported line (configs[1]), without the configs[2..4] lines attached to it")
+    ap.add_argument("--full", action="store_true", help="also what the reported line does not need (N = 1 only): the configs[2..4] lines attached to "
+                    "the default cornell_box line and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: only the reported line (configs[1]), without the configs[2..4] lines attached to it")
     ap.add_argument("--workload", choices=["cornell_box", "smallpt", "dragon", "tr15_like"], default="cornell_box",
                     help="cornell_box = BASELINE.json configs[1] (the reported line); smallpt = configs[2] at 4096 spp; "
                          "dragon = configs[3] stand-in (871 200 triangles + MERL) at 2048 spp; tr15_like = configs[4] stand-in "
@@ -204,9 +209,21 @@ def main():
     ap.add_argument("--frames", type=int, default=1, help="tr15_like only: a step renders the SEQUENCE of frames [frame, frame + frames) -- the device scene moves from "
                     "frame to frame with tray_scene_update_frame (Scene::update_frame, scene.rs:152-176) inside the timed region; with N GPUs the frames are "
                     "dealt round-robin over the ranks (multi.shard_frames, BASELINE.json configs[4]), each rank renders whole frames, no collective")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def extras(args, world):
+    """What a run does beyond the reported line: (configs[2..4] lines, CPU baseline). Nothing without --full."""
+    single = args.full and world == 1
+    others = single and args.workload == "cornell_box" and not args.spp and not args.no_other_workloads
+    return others, single and not args.no_cpu_baseline
+
+
+def main():
+    args = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -387,9 +404,10 @@ def main():
         }
         if args.dump_outputs is not None:
             out["dumped_outputs"] = {"dir": args.dump_outputs, "names": dumped}
-    # BASELINE.json configs[2..4] beside the reported line (N = 1 only, like the CPU leg): one warm-up launch at a cut-down sample
-    # count, then full-size frames -- so that the driver's own run sees every workload, not only cornell_box
-    if world == 1 and args.workload == "cornell_box" and not args.spp and not args.no_other_workloads:
+    other_workloads, with_cpu_baseline = extras(args, world)
+    # --full: BASELINE.json configs[2..4] beside the reported line (N = 1 only, like the CPU leg): one warm-up launch at a cut-down
+    # sample count, then full-size frames -- so that one run sees every workload, not only cornell_box
+    if other_workloads:
         others = []
         # (configs[4] is a SEQUENCE: the tr15 stand-in runs two consecutive frames per step, the device scene moved from one to the next with
         # tray_scene_update_frame inside the timed region; `frame_kernel_value` is the rate of the frames' kernels alone, HIP events)
@@ -407,7 +425,7 @@ def main():
             others.append(entry)
         out["workloads"] = others
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if with_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(main_m["scene"].flatten(main_m["frame"]), main_m["spp"])
         print(json.dumps(out), flush=True)
     if distributed:

@@ -351,6 +351,36 @@ int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shar
 int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp,
                                uint32_t sample_begin, uint32_t sample_end, uint64_t seed, float* rgbw_dev, void* stream);
 
+/* Render to a noise threshold: tiles [tile_start, tile_start+tile_count) of the max_spp-sample LowDiscrepancy frame, each tile sampled until
+ * its estimated error drops below `threshold` (tile_count == 0 selects the whole queue, as in tray_render_tiles_device).
+ * - Rounds. Round 0 renders the samples [0, min_spp) of every tile; round r >= 1 renders [min_spp 2^(r-1), min_spp 2^r) of the tiles that are
+ *   still active. Each tile t ends with a power-of-two prefix [0, n_t) of its samples, min_spp <= n_t <= max_spp. Sample s is the sample the
+ *   whole frame traces at s (tray_render_samples_device).
+ * - Films. A round's range [a, b) is split at m = (a + b) / 2: [a, m) is added into even_dev, [m, b) into odd_dev, both RGBW films in the
+ *   get_renderf32 layout that the caller zeroes beforehand. The image is even + odd: exactly the film of the samples [0, n_t) of every tile.
+ * - Error of a tile, after every round, from the two films: for each of its pixels inside the image, with E / O the pixel of even / odd,
+ *   e = E.rgb / E.w, o = O.rgb / O.w, d = (|e.r - o.r| + |e.g - o.g| + |e.b - o.b|) / 2, m = max(0, (sum(e) + sum(o)) / 2) and
+ *   err_p = d / (1e-4 + sqrt(m)); a pixel with E.w <= 0 or O.w <= 0 counts as +inf. The tile's error is the maximum over its pixels (NaN if
+ *   any pixel's is NaN): the two-buffer estimate of production renderers, relative to the square root of the pixel's brightness.
+ * - Stopping rule. A tile stays active while !(error < threshold) and n_t < max_spp: a NaN error keeps it active.
+ * - Outputs. tile_samples[i] / tile_error[i] (host arrays of tile_count entries, queue order) receive n_t and the tile's last error: the one
+ *   of the round it stopped in. Later rounds of its neighbours still add samples to its edge pixels (the reconstruction filter's footprint),
+ *   so that error is the metric of the returned films wherever no neighbouring tile took more samples.
+ *   TrayKernelTiming covers the whole call: the samples of all rounds, every launch, render_ms from its first to its last event. The call
+ *   synchronises on `stream` once per round (it reads the number of active tiles) and returns when it is done.
+ * - Border pixels. The reconstruction filter reaches across tile borders. With a filter that has negative lobes (Mitchell-Netravali), a
+ *   pixel next to tiles that ended with many times its tile's samples can get a total weight w near zero or below it, so that rgb / w
+ *   resolves to black or to a saturated value; a uniform render has no such pixel. Callers should treat pixels with w <= 0, or with rgb / w
+ *   far outside the image's range, as missing ("Rendering to a noise threshold": measured counts and the planned fix, a bound on
+ *   the ratio of n_t between neighbouring tiles).
+ * - Determinism. The films are sums of float atomics, so a tile whose error lies within rounding of `threshold` may be decided either way
+ *   from one run to the next. What the call returns is always the film of exactly the reported [0, n_t) of every tile.
+ * Returns TRAY_E_INVALID unless 2 <= min_spp <= max_spp are powers of two, threshold >= 0 (not NaN), no pointer is null and the two films are
+ * different buffers; TRAY_E_UNSUPPORTED while tray_scene_set_sampler has chosen Uniform or Adaptive. */
+int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp,
+                                    float threshold, uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples,
+                                    float* tile_error, void* stream);
+
 /* Host-side enumeration of the Morton-queue indices tray_render_shard_device renders for `shard`
  * (same mapping; lets callers and tests reason about the partition without a GPU). */
 int tray_shard_tiles(uint32_t n_tiles, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles,

@@ -285,6 +285,32 @@ class Hip:
                     self.last_timing = t
                 yield end, rt
 
+    def render_noise_target(self, scene, rt, config, threshold, min_spp=16):
+        """config.select_blocks of the frame rendered to a noise threshold (tray_render_noise_target_device): every tile takes the
+        power-of-two prefix [0, n_t) of the round_spp(config.spp)-sample LowDiscrepancy frame, min_spp <= n_t <= that spp, at which its
+        two-buffer error drops below `threshold`. The image (even + odd film) is added into rt. Returns (tile_samples, tile_error): numpy
+        arrays of n_t and the last error per tile, in BlockQueue order. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        import torch
+        dev = scene.device_scene(config.current_frame, self.device)
+        spp = self._select_sampler(dev, config.spp)
+        start, count = (int(v) for v in config.select_blocks)
+        w, h = rt.dimensions()
+        n = len(BlockQueue((w, h), (8, 8), (start, count)).blocks)
+        samples, error = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        with torch.cuda.device(self.device):
+            even = torch.zeros(h * w * 4, dtype=torch.float32, device=f"cuda:{self.device}")
+            odd = torch.zeros_like(even)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_render_noise_target_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
+                                                        C.c_void_p(odd.data_ptr()), samples.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                        error.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(stream) if stream else None))
+            rt.add_pixels((even + odd).cpu().numpy())
+        t = _lib.TrayKernelTiming()
+        if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
+            self.last_timing = t
+            print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
+        return samples, error
+
     def render_shard_device(self, scene, frame, shard, n_shards, spp, rgbw_ptr, chunk_tiles=16, stream=None):
         """One rank's share of a frame (round-robin chunks of the Morton queue); merge = sum over ranks."""
         dev = scene.device_scene(frame, self.device)

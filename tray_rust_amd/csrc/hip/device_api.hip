@@ -7,6 +7,7 @@
 #define TR_INST_EXTERN   // explicit instantiation declarations of every kernel the launch sites below name
 #include "kernel_list.h"
 #include "kernel_ranges.h"
+#include "noise.h"
 #undef TR_INST_EXTERN
 
 
@@ -75,6 +76,16 @@ struct LaunchBuffers {
     bool last_used_table = false;        // the last launch read the table
     bool owns_any() const { return wf.ready || xf_cache || d_xf_table; }
 };
+// tray_render_noise_target_device's per-tile state, n_tiles entries each, in one allocation made on first use: the round's tile list (coordinates and
+// queue indices; the error kernel reads it before the compaction rewrites it, in stream order, so one list serves every round), the next-round flags,
+// the samples taken and the errors (by queue index), and the list's length; h_count is the pinned word the host reads it into once per round
+struct NoiseBuffers {
+    void* mem = nullptr;
+    uint2* list = nullptr;
+    uint32_t* list_q = nullptr, * active = nullptr, * samples = nullptr, * d_count = nullptr;
+    float* err = nullptr;
+    uint32_t* h_count = nullptr;
+};
 struct TrayDeviceScene {
     int device = 0;
     DevScene dev{};
@@ -128,6 +139,8 @@ struct TrayDeviceScene {
     uint32_t sampler_kind = TRAY_SAMPLER_LOW_DISCREPANCY, smp_min = 1, smp_max = 1;
     void* d_smp = nullptr;            // [state u32 | running average f32 | luminances f32 x cap] per pixel of a batch of tiles
     size_t smp_bytes = 0;
+    NoiseBuffers nt;                  // tray_render_noise_target_device (allocated on first use, kept across frame updates)
+    bool accumulate = false;          // a tray_render_noise_target_device call is running: its launches add to one set of stats, between its own events
 };
 
 static thread_local int g_device = 0;
@@ -369,6 +382,8 @@ void tray_scene_destroy(TrayDeviceScene* s) {
     for (void* p : s->allocs) (void)hipFree(p);
     lb_drop(s->lb, LB_ALL);
     if (s->d_smp) (void)hipFree(s->d_smp);
+    if (s->nt.mem) (void)hipFree(s->nt.mem);
+    if (s->nt.h_count) (void)hipHostFree(s->nt.h_count);
     for (int k = 0; k < WF_PIPES_MAX; ++k) {
         if (s->wf_streams[k]) (void)hipStreamDestroy(s->wf_streams[k]);
         if (s->wf_join[k]) (void)hipEventDestroy(s->wf_join[k]);
@@ -865,13 +880,16 @@ int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* f) {
     }
     n->sampler_kind = s->sampler_kind; n->smp_min = s->smp_min; n->smp_max = s->smp_max;   // (tray_scene_set_sampler belongs to the handle)
     std::swap(n->d_smp, s->d_smp); std::swap(n->smp_bytes, s->smp_bytes);
+    std::swap(n->nt, s->nt);
     std::swap(*s, *n);        // the handle keeps its identity; n now owns what the new frame did not take over
     tray_scene_destroy(n);
     return TRAY_OK;
 }
 
+// tiles: the launch's tile list in device memory (a sub-range of s->d_tiles, or tray_render_noise_target_device's list of active tiles); work item w renders
+// tiles[(w / chunk) * chunk_stride * chunk + (w % chunk)].
 // smp_begin / smp_end: the sample range [smp_begin, smp_end) of the spp-sample LowDiscrepancy frame to render (tray_render_samples_device); 0 / 0 = all of [0, spp)
-static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
+static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                         uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_, uint32_t smp_begin = 0u, uint32_t smp_end = 0u);
 
 // every buffer of the wavefront schedule for a pool of n_slots; on failure nothing stays allocated and TRAY_E_NOMEM is returned
@@ -946,7 +964,7 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
 
 // Wavefront schedule: rounds of six stage kernels over the path pool until every tile is done.
 // The host only polls a "tiles done" word every WF_POLL rounds; kernels of finished chunks exit at once.
-static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
+static int launch_wavefront(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                             uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     const WfBuffers& w = s->lb.wf;
     const uint32_t n = smp_end ? smp_end - smp_begin : spp;   // samples per pixel this launch renders: the rules below cut them (a slice is never empty: 2^slice_shift <= n)
@@ -965,8 +983,7 @@ static int launch_wavefront(TrayDeviceScene* s, uint32_t tile_start, uint32_t ti
         HIP_CHECK(hipMemcpyAsync(w.d_chunks, init.data(), (size_t)n_chunks * sizeof(WfChunk), hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));   // `init` is pageable host memory
     }
-    HIP_CHECK(hipEventRecord(s->ev0, stream));
-    const uint2* tiles = s->d_tiles + tile_start;
+    if (!s->accumulate) HIP_CHECK(hipEventRecord(s->ev0, stream));
     uint32_t launches = 0;
     // the views: equal shares of the chunks in use. Measured on the C5 stand-in at full detail (1 / 2 / 3 / 4 views): see DESIGN.md section 4
     // (with rounds of 24 M slots and more one view is ahead: C5 stand-in 155.8 against 152.9 Msamples/s at 32 M; at 16 M two views 146.8 against 144.3)
@@ -1064,7 +1081,7 @@ int tray_render_tiles_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t t
     if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // BlockQueue::new ignores `start` when count == 0 (block_queue.rs:39-41), like tray_block_queue
     if (tile_start > s->n_tiles) tile_start = s->n_tiles;                       // skip(start).take(count)
     if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
-    return launch_tiles(s, tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_);
+    return launch_tiles(s, s->d_tiles + tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_);
 }
 
 int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles, uint32_t spp, uint64_t seed,
@@ -1074,12 +1091,12 @@ int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shar
     // chunks c = shard, shard + n_shards, ... of chunk_tiles tiles each; the last chunk may be short
     uint32_t n_chunks = (s->n_tiles + chunk_tiles - 1) / chunk_tiles;
     uint32_t my_chunks = shard < n_chunks ? (n_chunks - shard + n_shards - 1) / n_shards : 0;
-    if (my_chunks == 0) return launch_tiles(s, 0, 0, 1, 1, spp, seed, rgbw_dev, stream_);
+    if (my_chunks == 0) return launch_tiles(s, s->d_tiles, 0, 1, 1, spp, seed, rgbw_dev, stream_);
     uint32_t last_chunk = shard + (my_chunks - 1) * n_shards;
     uint32_t tail = s->n_tiles - last_chunk * chunk_tiles;   // tiles in my last chunk
     if (tail > chunk_tiles) tail = chunk_tiles;
     uint32_t work = (my_chunks - 1) * chunk_tiles + tail;
-    return launch_tiles(s, shard * chunk_tiles, work, chunk_tiles, n_shards, spp, seed, rgbw_dev, stream_);
+    return launch_tiles(s, s->d_tiles + shard * chunk_tiles, work, chunk_tiles, n_shards, spp, seed, rgbw_dev, stream_);
 }
 
 int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint32_t sample_begin, uint32_t sample_end,
@@ -1091,7 +1108,85 @@ int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t
     if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // as tray_render_tiles_device
     if (tile_start > s->n_tiles) tile_start = s->n_tiles;
     if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
-    return launch_tiles(s, tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
+    return launch_tiles(s, s->d_tiles + tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
+}
+
+// tray_render_noise_target_device's rounds over queue[0, tile_count) (include/trayhip.h), with s->accumulate set: round r renders [a, b) --
+// [0, min_spp), then [min_spp 2^(r-1), min_spp 2^r) -- of the active tiles, [a, m) into even and [m, b) into odd, then k_noise_error writes every
+// active tile's error, samples and flag, k_noise_compact the next list in queue order, and the host reads its length once.
+static int noise_rounds(TrayDeviceScene* s, const uint2* queue, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold, uint64_t seed,
+                        float* even_dev, float* odd_dev, hipStream_t stream, uint32_t* launches) {
+    NoiseBuffers& b = s->nt;
+    const uint2* list = queue;        // round 0: the whole range, queue index = list index
+    const uint32_t* list_q = nullptr;
+    uint32_t n_active = tile_count;
+    for (uint32_t lo = 0u, hi = min_spp;; lo = hi, hi *= 2u) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        int rc = launch_tiles(s, list, n_active, n_active, 1u, max_spp, seed, even_dev, stream, lo, mid);
+        if (rc != TRAY_OK) return rc;
+        *launches += s->launches;
+        rc = launch_tiles(s, list, n_active, n_active, 1u, max_spp, seed, odd_dev, stream, mid, hi);
+        if (rc != TRAY_OK) return rc;
+        *launches += s->launches;
+        tr_noise::error(stream, even_dev, odd_dev, s->dev.width, s->dev.height, list, list_q, n_active, hi, max_spp, threshold, b.err, b.active, b.samples);
+        tr_noise::compact(stream, queue, b.active, tile_count, b.list, b.list_q, b.d_count);
+        *launches += 2u;
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(b.h_count, b.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        n_active = *b.h_count;
+        if (n_active > tile_count) { set_error("tray_render_noise_target_device: the compacted tile list is longer than the queue"); return TRAY_E_DEVICE; }
+        if (n_active == 0u || hi >= max_spp) return TRAY_OK;   // (at max_spp no flag is set: n_active is 0 there too)
+        list = b.list; list_q = b.list_q;
+    }
+}
+
+int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
+                                    uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
+    if (!s || !even_dev || !odd_dev || !tile_samples || !tile_error) { set_error("tray_render_noise_target_device: null argument"); return TRAY_E_INVALID; }
+    auto pow2 = [](uint32_t v) { return v != 0u && (v & (v - 1u)) == 0u; };
+    if (!pow2(min_spp) || !pow2(max_spp) || min_spp < 2u || max_spp < min_spp) {
+        set_error("tray_render_noise_target_device: min_spp and max_spp must be powers of two with 2 <= min_spp <= max_spp"); return TRAY_E_INVALID;
+    }
+    if (!(threshold >= 0.0f)) { set_error("tray_render_noise_target_device: threshold must be >= 0 (and not NaN)"); return TRAY_E_INVALID; }
+    if (even_dev == odd_dev) { set_error("tray_render_noise_target_device: the even and odd films must be different buffers"); return TRAY_E_INVALID; }
+    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error("tray_render_noise_target_device: sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
+    if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
+    if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // as tray_render_tiles_device
+    if (tile_start > s->n_tiles) tile_start = s->n_tiles;
+    if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HIP_CHECK(hipSetDevice(s->device));
+    s->timing_valid = false;
+    s->empty_launch = false;
+    if (tile_count == 0) { std::fprintf(stderr, "Warning: This block queue is empty!\n"); s->empty_launch = true; return TRAY_OK; }   // block_queue.rs:42-44
+    NoiseBuffers& b = s->nt;
+    if (!b.mem) {   // [list: uint2 | list_q | active | samples | err: u32 / f32 | count], n_tiles entries each
+        const size_t n = s->n_tiles;
+        HIP_CHECK(hipMalloc(&b.mem, n * (sizeof(uint2) + 4u * sizeof(uint32_t)) + sizeof(uint32_t)));
+        b.list = static_cast<uint2*>(b.mem);
+        b.list_q = reinterpret_cast<uint32_t*>(b.list + n);
+        b.active = b.list_q + n;
+        b.samples = b.active + n;
+        b.err = reinterpret_cast<float*>(b.samples + n);
+        b.d_count = reinterpret_cast<uint32_t*>(b.err + n);
+    }
+    if (!b.h_count) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.h_count), sizeof(uint32_t), hipHostMallocDefault));
+    HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));   // (the launches below add to them: s->accumulate)
+    HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
+    HIP_CHECK(hipEventRecord(s->ev0, stream));
+    uint32_t launches = 0u;
+    s->accumulate = true;
+    const int rc = noise_rounds(s, s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, stream, &launches);
+    s->accumulate = false;
+    if (rc != TRAY_OK) { s->timing_valid = false; return rc; }
+    HIP_CHECK(hipEventRecord(s->ev1, stream));
+    HIP_CHECK(hipMemcpyAsync(tile_samples, b.samples, (size_t)tile_count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(tile_error, b.err, (size_t)tile_count * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    s->launches = launches;
+    s->timing_valid = true;
+    return TRAY_OK;
 }
 
 int tray_multi_shard_samples(uint32_t spp, uint32_t d, uint32_t n_dev, uint32_t* begin, uint32_t* end) {
@@ -1105,7 +1200,7 @@ int tray_multi_shard_samples(uint32_t spp, uint32_t d, uint32_t n_dev, uint32_t*
 
 // thread_work with sampler::Uniform / sampler::Adaptive (include/trayhip.h: tray_scene_set_sampler): rounds of k_sampler_pass (+
 // k_sampler_decide) over batches of tiles, all on `stream`, no host synchronisation -- a pixel that is finished sits out the later rounds.
-static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
+static int launch_sampler(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                           uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     SamplerPass sp{};
     sp.kind = s->sampler_kind; sp.min_spp = s->smp_min; sp.max_spp = s->smp_max;
@@ -1131,7 +1226,7 @@ static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile
     uint32_t* const px_state = static_cast<uint32_t*>(s->d_smp);
     float* const px_avg = reinterpret_cast<float*>(px_state + (size_t)batch * 64u);
     float* const px_lum = px_avg + (size_t)batch * 64u;
-    HIP_CHECK(hipEventRecord(s->ev0, stream));
+    if (!s->accumulate) HIP_CHECK(hipEventRecord(s->ev0, stream));
     uint32_t launches = 0;
     for (uint32_t item0 = 0; item0 < tile_count; item0 += batch) {
         const uint32_t n_items = std::min(batch, tile_count - item0), n_px = n_items * 64u;
@@ -1148,10 +1243,10 @@ static int launch_sampler(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile
             uint32_t group = std::max(1u, std::min<uint32_t>(SP_GROUP_MAX, 4096u / per_tile));
             if (const char* ge = getenv("TRAYHIP_SAMPLER_GROUP")) group = (uint32_t)std::max(1, std::min(SP_GROUP_MAX, atoi(ge)));   // (measurement)
             const dim3 grid((n_items + group - 1u) / group), block(TR_BLOCK);
-#define SAMPLER_PASS(A, F) hipLaunchKernelGGL((k_sampler_pass<A, F>), grid, block, s->stack_bytes, stream, s->dev, s->d_tiles + tile_start, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group)
+#define SAMPLER_PASS(A, F) hipLaunchKernelGGL((k_sampler_pass<A, F>), grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group)
             const bool lean = s->feat == FEAT_NONE && s->dev.integrator != TRAY_INTEGRATOR_WHITTED;   // (no optional lobe, no texture: the small instantiation)
             if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY && smp_end)
-                tr_ranges::sampler_pass(s->deforming ? 3 : s->animated ? 2 : 0, lean, grid, block, s->stack_bytes, stream, s->dev, s->d_tiles + tile_start, item0, n_items, chunk,
+                tr_ranges::sampler_pass(s->deforming ? 3 : s->animated ? 2 : 0, lean, grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk,
                                         chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group, smp_begin);
             else if (s->deforming) { if (lean) SAMPLER_PASS(3, FEAT_NONE); else SAMPLER_PASS(3, FEAT_ALL | FEAT_TEX); }
             else if (s->animated) { if (lean) SAMPLER_PASS(2, FEAT_NONE); else SAMPLER_PASS(2, FEAT_ALL | FEAT_TEX); }
@@ -1292,7 +1387,7 @@ static int launch_prepare(TrayDeviceScene* s, uint64_t samples, hipStream_t stre
     return TRAY_OK;
 }
 
-static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
+static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                         uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_, uint32_t smp_begin, uint32_t smp_end) {
     if (s->sampler_kind == TRAY_SAMPLER_LOW_DISCREPANCY && (spp == 0 || (spp & (spp - 1)) != 0)) {
         set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID;
@@ -1306,8 +1401,10 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     // instead of "no launch recorded", which made tray_multi_timing fail for 48 tiles on 8 devices: found by tests/test_multi_stub.py)
     if (tile_count == 0) { std::fprintf(stderr, "Warning: This block queue is empty!\n"); s->empty_launch = true; return TRAY_OK; }   // block_queue.rs:42-44
     HIP_CHECK(hipMemsetAsync(s->d_counter, 0, sizeof(uint32_t), stream));
-    HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));
-    HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
+    if (!s->accumulate) {   // (tray_render_noise_target_device clears them once for all its launches)
+        HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));
+        HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
+    }
     // key_frame on the host (same mixing as the device function)
     auto mix = [](uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; };
     uint32_t kf = mix((uint32_t)seed + 0x9E3779B9u);
@@ -1315,7 +1412,7 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     kf = mix(kf + s->dev.frame);
     if (smp_begin == 0u && smp_end == spp) smp_end = 0u;   // (the whole frame as a range: the whole-frame launch)
     const uint32_t n_smp = smp_end ? smp_end - smp_begin : spp;   // samples per pixel of this launch
-    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
+    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
     s->last_was_wavefront = false;
     const bool had_pool = s->lb.wf.ready;
     {
@@ -1328,7 +1425,7 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     }
     if (s->wavefront) {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = launch_wavefront(s, tile_start, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
+        const int rc = launch_wavefront(s, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] wavefront launch enqueued in %.1f ms (pool %s: %u slots)\n",
                                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
         return rc;
@@ -1359,17 +1456,17 @@ static int launch_tiles(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_c
     }
     s->launch_dev.sample_dump = static_cast<float4*>(dump_buf);
 #endif
-    HIP_CHECK(hipEventRecord(s->ev0, stream));
-#define PATH_TILES_L(A, F, L) hipLaunchKernelGGL((k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, L>), dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, s->d_tiles + tile_start, \
+    if (!s->accumulate) HIP_CHECK(hipEventRecord(s->ev0, stream));
+#define PATH_TILES_L(A, F, L) hipLaunchKernelGGL((k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, L>), dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, tiles, \
                                                  tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats)
 #define PATH_TILES(A, F) do { if (s->light_filter) PATH_TILES_L(A, F, true); else PATH_TILES_L(A, F, false); } while (0)
 #define PATH_TILES_F(A) do { if (s->feat == FEAT_NONE) PATH_TILES(A, FEAT_NONE); else if (s->feat == FEAT_MERL) PATH_TILES(A, FEAT_MERL); \
                              else if (s->feat == FEAT_SPEC) PATH_TILES(A, FEAT_SPEC); else if (s->feat == (FEAT_MERL | FEAT_SPEC)) PATH_TILES(A, FEAT_MERL | FEAT_SPEC); \
                              else if (s->feat == (FEAT_ALL | FEAT_TEX)) PATH_TILES(A, FEAT_ALL | FEAT_TEX); else PATH_TILES(A, FEAT_ALL); } while (0)
 #define WHITTED_TILES(A) hipLaunchKernelGGL((k_path_tiles<A, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>), dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, \
-                                             s->d_tiles + tile_start, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats)
+                                             tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats)
     if (smp_end) tr_ranges::path_tiles(s->animated ? 1 : 0, s->feat, s->dev.integrator == TRAY_INTEGRATOR_WHITTED, s->light_filter, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream,
-                                       s->launch_dev, s->d_tiles + tile_start, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats, smp_begin, smp_end);
+                                       s->launch_dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats, smp_begin, smp_end);
     else if (s->dev.integrator == TRAY_INTEGRATOR_WHITTED) { if (s->animated) WHITTED_TILES(1); else WHITTED_TILES(0); }
     else if (s->animated) PATH_TILES_F(1);
     else PATH_TILES_F(0);
@@ -1583,7 +1680,7 @@ int tray_render_frame_multi(TrayMultiScene* m, uint32_t spp, uint64_t seed, floa
                 uint32_t b = 0u, e = 0u;
                 (void)tray_multi_shard_samples(spp, (uint32_t)d, (uint32_t)m->n_dev, &b, &e);
                 rcs[d] = b < e ? tray_render_samples_device(m->scenes[d], 0u, 0u, spp, b, e, seed, m->films[d], m->streams[d])
-                               : launch_tiles(m->scenes[d], 0, 0, 1, 1, spp, seed, m->films[d], m->streams[d]);   // (an empty range: no launch, the film joins the reduce as zeros)
+                               : launch_tiles(m->scenes[d], m->scenes[d]->d_tiles, 0, 1, 1, spp, seed, m->films[d], m->streams[d]);   // (an empty range: no launch, the film joins the reduce as zeros)
             } else {
                 rcs[d] = tray_render_shard_device(m->scenes[d], (uint32_t)d, (uint32_t)m->n_dev, 16u, spp, seed, m->films[d], m->streams[d]);
             }

@@ -79,6 +79,13 @@ NOINSTR int emu_profile_dump(const char* path) {
 #endif
 
 #include "../../tray_rust_amd/csrc/hip/kernels.hip"
+#include "../../tray_rust_amd/csrc/hip/kernel_select.h"   // the library's choice of the instantiation ...
+#include "../../tray_rust_amd/csrc/hip/launch_rules.h"    // ... and its launch rules: the emulation applies them, it has no copy
+#ifdef TR_SAMPLE_RANGES   // (emu_sample_ranges.cpp) the kernels take a sample range: EMU_RANGE appends it to a call, and only there do the two builds differ
+#define EMU_RANGE(...) , __VA_ARGS__
+#else
+#define EMU_RANGE(...)
+#endif
 
 namespace trayh { void set_error(const std::string&) {} }
 
@@ -120,6 +127,14 @@ uint32_t bvh_depth(const TrayBvhNode* nodes, uint32_t n) {
 static bool deforming(const TrayFlatScene* f) {
     for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].geom_type == TRAY_GEOM_ANIMATED_MESH) return true;
     return false;
+}
+
+// ... or anything that needs ray.time: the ANIM = 1 / 2 instantiations (tray_scene_create: TrayDeviceScene::animated)
+static bool scene_moves(const TrayFlatScene* f) {
+    bool moving = f->camera.animated != 0;
+    for (uint32_t t_ = 0; t_ < f->n_textures; ++t_) moving = moving || f->textures[t_].n_frames >= 2u;   // animated_image needs ray.time
+    for (uint32_t i = 0; i < f->n_instances; ++i) moving = moving || f->instances[i].animated != 0 || f->instances[i].emis_count >= 2;
+    return moving;
 }
 
 void make_scene(const TrayFlatScene* f, EmuScene& e) {
@@ -181,12 +196,6 @@ bool film_rows_ok(const TrayFlatScene* f) {
             if (f->film.table[y * TRAY_FILTER_TABLE_SIZE + x] != f->film.table_x[x] * f->film.table_y[y]) { ok = false; break; }
     return ok;
 }
-uint32_t key_frame_host(uint64_t seed, uint32_t frame) {   // as launch_tiles computes it
-    auto mix = [](uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; };
-    uint32_t kf = mix((uint32_t)seed + 0x9E3779B9u);
-    kf = mix(kf ^ (uint32_t)(seed >> 32));
-    return mix(kf + frame);
-}
 
 }  // namespace
 
@@ -207,65 +216,48 @@ int emu_debug_sample_radiance(const TrayFlatScene* f, uint32_t n, const uint32_t
                               uint64_t seed, float* out) {
     EmuScene e;
     make_scene(f, e);
-    const uint32_t kf = key_frame_host(seed, e.d.frame);
-    bool moving = f->camera.animated != 0;
-    for (uint32_t t_ = 0; t_ < f->n_textures; ++t_) moving = moving || f->textures[t_].n_frames >= 2u;   // animated_image needs ray.time (tray_scene_create)
-    for (uint32_t i = 0; i < f->n_instances; ++i) moving = moving || f->instances[i].animated != 0 || f->instances[i].emis_count >= 2;
+    const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
+    const bool moving = scene_moves(f);
     if (deforming(f)) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<3>(e.d, n, px, py, si, spp, kf, out); });
     else if (moving) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<2>(e.d, n, px, py, si, spp, kf, out); });
     else launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<0>(e.d, n, px, py, si, spp, kf, out); });
     return 0;
 }
 
-// launch_sampler (kernels.hip) for the tiles given: thread_work with sampler::Uniform / sampler::Adaptive. batch_tiles bounds the tiles per
-// batch (0 = all at once), so that tests can see batches add up. stats_out: samples, vertices, rays.
-int emu_render_sampler(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t kind, uint32_t min_spp, uint32_t max_spp,
-                       uint64_t seed, float* rgbw, uint32_t batch_tiles, unsigned long long* stats_out) {
+// launch_sampler (device_api.hip) for the tiles given: thread_work with sampler::Uniform / sampler::Adaptive, or LowDiscrepancy (min_spp = the render's
+// spp) over the samples [smp_begin, smp_end) of the frame, 0 / 0 = all of them. batch_tiles bounds the tiles per batch (0 = all at once), so that tests
+// can see batches add up. stats_out: samples, vertices, rays.
+static int render_sampler(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t kind, uint32_t min_spp, uint32_t max_spp,
+                          uint32_t smp_begin, uint32_t smp_end, uint64_t seed, float* rgbw, uint32_t batch_tiles, unsigned long long* stats_out) {
     EmuScene e;
     make_scene(f, e);
-    const uint32_t kf = key_frame_host(seed, e.d.frame);
-    bool moving = f->camera.animated != 0;
-    for (uint32_t t_ = 0; t_ < f->n_textures; ++t_) moving = moving || f->textures[t_].n_frames >= 2u;
-    for (uint32_t i = 0; i < f->n_instances; ++i) moving = moving || f->instances[i].animated != 0 || f->instances[i].emis_count >= 2;
+    const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
+    const bool moving = scene_moves(f);
     std::vector<uint2> tiles(tile_count);
     for (uint32_t i = 0; i < tile_count; ++i) tiles[i] = make_uint2(tiles_xy[2 * i], tiles_xy[2 * i + 1]);
     DevStats stats;
     std::memset(&stats, 0, sizeof stats);
-    auto round_up = [](uint32_t v) { uint32_t p = 1; while (p < v && p < 0x80000000u) p <<= 1; return p; };
+    if (kind > TRAY_SAMPLER_ADAPTIVE) return -1;
     SamplerPass sp{};
-    sp.kind = kind; sp.min_spp = round_up(min_spp); sp.max_spp = round_up(max_spp);
-    uint32_t rounds = 1;
-    if (kind == TRAY_SAMPLER_ADAPTIVE) {
-        if (sp.max_spp < sp.min_spp) return -1;
-        sp.step = round_up((sp.max_spp - sp.min_spp) / 5u);
-        while (sp.min_spp + (rounds - 1u) * sp.step < sp.max_spp) ++rounds;
-        sp.lum_cap = sp.min_spp + (rounds - 1u) * sp.step;
-    } else if (kind == TRAY_SAMPLER_UNIFORM) { sp.min_spp = sp.max_spp = 1u; sp.step = 1u; sp.lum_cap = 0u; }
-    else if (kind == TRAY_SAMPLER_LOW_DISCREPANCY) { sp.max_spp = sp.min_spp; sp.step = 1u; sp.lum_cap = 0u; }   // (scenes with an AnimatedMesh: min_spp = the render's spp)
-    else return -1;
+    sp.kind = kind; sp.min_spp = tr_rules::round_spp(min_spp); sp.max_spp = tr_rules::round_spp(max_spp);   // (tray_scene_set_sampler)
+    if (kind == TRAY_SAMPLER_ADAPTIVE && sp.max_spp < sp.min_spp) return -1;
+    tr_rules::whole_frame_range(min_spp, smp_begin, smp_end);
+    const uint32_t rounds = tr_rules::sampler_plan(sp, sp.min_spp);
     const uint32_t batch = batch_tiles ? std::min(batch_tiles, std::max(tile_count, 1u)) : std::max(tile_count, 1u);
     std::vector<uint32_t> px_state((size_t)batch * 64u);
     std::vector<float> px_avg((size_t)batch * 64u), px_lum((size_t)batch * 64u * std::max(sp.lum_cap, 1u));
-    const uint32_t chunk = tile_count ? tile_count : 1u;
+    const uint32_t chunk = tr_rules::whole_queue(tile_count).chunk;
     int rc = 0;   // (the window is shared by the block's threads: a SIMT emulation, as for k_path_tiles)
     for (uint32_t item0 = 0; item0 < tile_count; item0 += batch) {
         const uint32_t n_items = std::min(batch, tile_count - item0), n_px = n_items * 64u;
         std::fill(px_state.begin(), px_state.end(), 0u); std::fill(px_avg.begin(), px_avg.end(), 0.0f);
         for (uint32_t j = 0; j < rounds; ++j) {
-            sp.pass = j;
-            sp.count = kind == TRAY_SAMPLER_ADAPTIVE ? (j == 0u ? sp.min_spp : sp.step) : sp.min_spp;
-            sp.taken = kind == TRAY_SAMPLER_ADAPTIVE ? sp.min_spp + j * sp.step : 0u;
-            sp.before = j == 0u ? 0u : sp.min_spp + (j - 1u) * sp.step;
-            const uint32_t per_tile = 64u * sp.count;   // launch_sampler's groups of tiles
-            uint32_t group = std::max(1u, std::min<uint32_t>(SP_GROUP_MAX, 4096u / per_tile));
-            if (const char* ge = getenv("TRAYHIP_SAMPLER_GROUP")) group = (uint32_t)std::max(1, std::min(SP_GROUP_MAX, atoi(ge)));   // (tests: ragged groups)
+            tr_rules::sampler_round(sp, j, smp_end ? smp_end - smp_begin : 0u);
+            const uint32_t group = tr_rules::sampler_group(sp.count, SP_GROUP_MAX);
             const uint32_t grid = (n_items + group - 1u) / group;
-#define EMU_SAMPLER_PASS(A, F) rc = launch_simt(grid, TR_BLOCK, [&] { k_sampler_pass<A, F>(e.d, tiles.data(), item0, n_items, chunk, 1u, kf, sp, px_state.data(), px_lum.data(), rgbw, &stats, group); })
-            const bool lean = feature_set(e) == FEAT_NONE && f->integrator != TRAY_INTEGRATOR_WHITTED;   // launch_sampler's choice of the instantiation
-            if (deforming(f)) { if (lean) EMU_SAMPLER_PASS(3, FEAT_NONE); else EMU_SAMPLER_PASS(3, FEAT_ALL | FEAT_TEX); }
-            else if (moving) { if (lean) EMU_SAMPLER_PASS(2, FEAT_NONE); else EMU_SAMPLER_PASS(2, FEAT_ALL | FEAT_TEX); }
-            else { if (lean) EMU_SAMPLER_PASS(0, FEAT_NONE); else EMU_SAMPLER_PASS(0, FEAT_ALL | FEAT_TEX); }
-#undef EMU_SAMPLER_PASS
+            select_sampler_pass(deforming(f) ? 3 : moving ? 2 : 0, sampler_lean(feature_set(e), f->integrator), [&](auto kernel) {
+                rc = launch_simt(grid, TR_BLOCK, [&] { kernel(e.d, tiles.data(), item0, n_items, chunk, 1u, kf, sp, px_state.data(), px_lum.data(), rgbw, &stats, group EMU_RANGE(smp_begin)); });
+            });
             if (rc != 0) return -3;
             if (kind == TRAY_SAMPLER_ADAPTIVE)
                 launch((n_px + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_sampler_decide(n_px, sp, px_state.data(), px_avg.data(), px_lum.data()); });
@@ -274,12 +266,16 @@ int emu_render_sampler(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_
     if (stats_out) { stats_out[0] = stats.samples; stats_out[1] = stats.vertices; stats_out[2] = stats.rays; }
     return 0;
 }
+int emu_render_sampler(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t kind, uint32_t min_spp, uint32_t max_spp,
+                       uint64_t seed, float* rgbw, uint32_t batch_tiles, unsigned long long* stats_out) {
+    return render_sampler(f, tiles_xy, tile_count, kind, min_spp, max_spp, 0u, 0u, seed, rgbw, batch_tiles, stats_out);
+}
 
 // Debugging aid: the loop of k_debug_sample_radiance<0> for ONE sample with the lane state printed after every vertex
 int emu_trace_sample(const TrayFlatScene* f, uint32_t px, uint32_t py, uint32_t si, uint32_t spp, uint64_t seed) {
     EmuScene e;
     make_scene(f, e);
-    const uint32_t kf = key_frame_host(seed, e.d.frame);
+    const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
     hip_emu::launch(1, 1, [&] {
         const DevScene& sc = e.d;
         TR_DYN_LDS(uint32_t, s_stack);
@@ -358,7 +354,7 @@ int emu_wf_trace(const TrayFlatScene* f, int stage, uint32_t n, const TrayRay* r
     std::vector<uint32_t> fallback((size_t)n_slots * WF_RAY_WORDS, 0u);   // records of the deferred rays (on the device: the buffer of a ray queue that is idle during the stage)
     std::vector<DevStats> stats(WF_STAT_SLOTS);
     std::memset(stats.data(), 0, stats.size() * sizeof(DevStats));
-    // (the traversal, then the rays it handed to the reference's binary traversal: wf_round of kernels.hip)
+    // (the traversal, then the rays it handed to the reference's binary traversal: wf_round of device_api.hip)
 #define EMU_TRACE(S) do { launch(blocks, TR_BLOCK, [&] { k_wf_trace_dyn<S, 0>(e.d, pool, queue.data(), qctl.data(), stats.data(), lds_depth, overflow.data(), fallback.data(), 0u); }); \
                           launch(2, TR_BLOCK, [&] { k_wf_trace_fallback<S, 0>(e.d, pool, qctl.data(), fallback.data(), 0u); }); } while (0)
     if (stage == 0) EMU_TRACE(0); else if (stage == 1) EMU_TRACE(1); else EMU_TRACE(2);
@@ -373,7 +369,7 @@ int emu_wf_trace(const TrayFlatScene* f, int stage, uint32_t n, const TrayRay* r
     return 0;
 }
 
-// TRAYHIP_EMU_XF_TABLE=1: the frame's transform table (device_api.hip: xf_table_prepare, k_xf_table_build) under the emulated kernels. The table of all
+// TRAYHIP_EMU_XF_TABLE=1: the frame's transform table (device_api.hip: xf_table_ensure, k_xf_table_build) under the emulated kernels. The table of all
 // 2^24 shutter-time indices is 2 GB per moving instance: here it is a sparse mapping whose records exist for the indices the rendered (pixel, sample)
 // pairs draw -- evaluated with k_xf_table_build's expressions --, which are the only ones the kernels read.
 struct SparseXfTable {
@@ -389,7 +385,7 @@ struct SparseXfTable {
         if (p == MAP_FAILED) return false;
         data = static_cast<float*>(p);
         std::vector<uint8_t> have((size_t)1 << 21, 0u);   // one bit per index
-        const uint32_t kf = key_frame_host(seed, frame);
+        const uint32_t kf = tr_rules::frame_key(seed, frame);
         const TrayCamera& c = f->camera;
         for (uint32_t i = 0; i < tile_count; ++i)
             for (uint32_t pix = 0; pix < 64u; ++pix) {
@@ -420,14 +416,12 @@ struct SparseXfTable {
 // as a SIMT emulation: 256 fibers per workgroup, wave intrinsics and barriers are rendezvous. rgbw is accumulated into.
 // coop / film_rows: -1 = as the library decides, 0 = off. Returns 0, or -3 if a rendezvous could not complete.
 // shard / n_shards / chunk_tiles: the launch tray_render_shard_device makes for one rank (chunks shard, shard + n_shards, ... of chunk_tiles
-// tiles each); n_shards = 0 renders the whole queue given.
-int emu_render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t spp, uint64_t seed, float* rgbw,
-                     uint32_t blocks, int coop, int film_rows, unsigned long long* stats_out, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles) {
+// tiles each); n_shards = 0 renders the whole queue given. [smp_begin, smp_end): the samples of the spp-sample frame to render, 0 / 0 = all of them.
+static int render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t spp, uint32_t smp_begin, uint32_t smp_end, uint64_t seed,
+                        float* rgbw, uint32_t blocks, int coop, int film_rows, unsigned long long* stats_out, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles) {
     EmuScene e;
     make_scene(f, e);
-    bool moving = f->camera.animated != 0;
-    for (uint32_t t_ = 0; t_ < f->n_textures; ++t_) moving = moving || f->textures[t_].n_frames >= 2u;   // animated_image needs ray.time (tray_scene_create)
-    for (uint32_t i = 0; i < f->n_instances; ++i) moving = moving || f->instances[i].animated != 0 || f->instances[i].emis_count >= 2;
+    const bool moving = scene_moves(f);
     if (f->n_instances > TR_FLAT_MAX && !moving) return -4;   // the library runs the wavefront schedule for those
     uint32_t n_moving = 0;
     for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].animated) ++n_moving;
@@ -453,68 +447,51 @@ int emu_render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t 
     else { e.d.win_offset = stack_words; stack_words += 4u * WIN_PLANE; }                               // ... or in its own region
     std::vector<uint2> tiles(tile_count);
     for (uint32_t i = 0; i < tile_count; ++i) tiles[i] = make_uint2(tiles_xy[2 * i], tiles_xy[2 * i + 1]);
-    // work-item mapping of launch_tiles: item w -> queue entry (w / chunk) * chunk_stride * chunk + (w % chunk), from tile_start on
-    uint32_t tile_start = 0, work = tile_count, chunk = tile_count ? tile_count : 1u, chunk_stride = 1u;
-    if (n_shards) {   // tray_render_shard_device
-        const uint32_t n_chunks = (tile_count + chunk_tiles - 1) / chunk_tiles;
-        const uint32_t my_chunks = shard < n_chunks ? (n_chunks - shard + n_shards - 1) / n_shards : 0;
-        if (my_chunks == 0) { if (stats_out) stats_out[0] = stats_out[1] = stats_out[2] = stats_out[3] = 0; return 0; }
-        const uint32_t last_chunk = shard + (my_chunks - 1) * n_shards;
-        uint32_t tail = tile_count - last_chunk * chunk_tiles;
-        if (tail > chunk_tiles) tail = chunk_tiles;
-        tile_start = shard * chunk_tiles; work = (my_chunks - 1) * chunk_tiles + tail; chunk = chunk_tiles; chunk_stride = n_shards;
-    }
+    const tr_rules::TileWork w = n_shards ? tr_rules::shard_work(tile_count, shard, n_shards, chunk_tiles) : tr_rules::whole_queue(tile_count);   // tray_render_shard_device
+    if (n_shards && w.work == 0u) { if (stats_out) stats_out[0] = stats_out[1] = stats_out[2] = stats_out[3] = 0; return 0; }
     uint32_t counter = 0;
     DevStats stats;
     std::memset(&stats, 0, sizeof stats);
-    const uint32_t kf = key_frame_host(seed, e.d.frame);
+    const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
     const int feat = feature_set(e);
-    uint32_t levels = 1u;   // launch_tiles' rule: tiles are cut into progressive sample slices when there are few of them per workgroup
-    { const bool small = work < 12u * blocks; const uint32_t most = small ? 5u : 3u, least = small ? 64u : 256u; while (levels < most && (spp >> levels) >= least) ++levels; }
-    if (const char* e_ = getenv("TRAYHIP_TILE_SLICES")) { levels = 1u; const uint32_t want = (uint32_t)std::max(1, atoi(e_)); while (levels < want && (spp >> levels) >= 1u) ++levels; }
-    int rc;
+    tr_rules::whole_frame_range(spp, smp_begin, smp_end);
+    const uint32_t levels = tr_rules::tile_levels(w.work, blocks, tr_rules::range_samples(spp, smp_begin, smp_end));
+    int rc = 0;
     // tray_scene_create: the instantiation with mis_ray_filter for scenes with a sphere light or specular lobes
     bool light_filter = (feat & FEAT_SPEC) != 0;
     for (uint32_t l = 0; l < f->n_lights; ++l)
         if (f->instances[f->lights[l]].kind != TRAY_INST_POINT_EMITTER && f->instances[f->lights[l]].geom_type == TRAY_GEOM_SPHERE) light_filter = true;
-#define EMU_TILES_L(A, F, L) launch_simt(blocks, TR_BLOCK, [&] { k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, L>(e.d, tiles.data() + tile_start, work, chunk, chunk_stride, spp, kf, levels, rgbw, &counter, &stats); }, (size_t)stack_words * 4)
-#define EMU_TILES(F) rc = moving ? (light_filter ? EMU_TILES_L(1, F, true) : EMU_TILES_L(1, F, false)) : (light_filter ? EMU_TILES_L(0, F, true) : EMU_TILES_L(0, F, false))
-#define EMU_WHITTED(A) launch_simt(blocks, TR_BLOCK, [&] { k_path_tiles<A, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>(e.d, tiles.data() + tile_start, work, chunk, chunk_stride, spp, kf, levels, rgbw, &counter, &stats); }, (size_t)stack_words * 4)
-    if (e.d.integrator == TRAY_INTEGRATOR_WHITTED) rc = moving ? EMU_WHITTED(1) : EMU_WHITTED(0);   // launch_tiles: one instantiation per ANIM
-    else if (feat == FEAT_NONE) EMU_TILES(FEAT_NONE);
-    else if (feat == FEAT_MERL) EMU_TILES(FEAT_MERL);
-    else if (feat == FEAT_SPEC) EMU_TILES(FEAT_SPEC);
-    else if (feat == (FEAT_MERL | FEAT_SPEC)) EMU_TILES(FEAT_MERL | FEAT_SPEC);
-    else if (feat == (FEAT_ALL | FEAT_TEX)) EMU_TILES(FEAT_ALL | FEAT_TEX);
-    else EMU_TILES(FEAT_ALL);
-#undef EMU_TILES
-#undef EMU_TILES_L
-#undef EMU_WHITTED
+    const auto run = [&](auto kernel) {
+        rc = launch_simt(blocks, TR_BLOCK, [&] { kernel(e.d, tiles.data() + w.first, w.work, w.chunk, w.chunk_stride, spp, kf, levels, rgbw, &counter, &stats EMU_RANGE(smp_begin, smp_end)); },
+                         (size_t)stack_words * 4);
+    };
+    const bool whitted = e.d.integrator == TRAY_INTEGRATOR_WHITTED;
+    if (moving) select_path_tiles<1>(feat, whitted, light_filter, run); else select_path_tiles<0>(feat, whitted, light_filter, run);
     if (stats_out) { stats_out[0] = stats.samples; stats_out[1] = stats.vertices; stats_out[2] = stats.rays; stats_out[3] = (unsigned long long)feat; }
     return rc;
 }
+int emu_render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t spp, uint64_t seed, float* rgbw,
+                     uint32_t blocks, int coop, int film_rows, unsigned long long* stats_out, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles) {
+    return render_tiles(f, tiles_xy, tile_count, spp, 0u, 0u, seed, rgbw, blocks, coop, film_rows, stats_out, shard, n_shards, chunk_tiles);
+}
 
-// The wavefront schedule (launch_wavefront + wf_round of kernels.hip): rounds of k_wf_advance -> k_wf_regen -> trace A ->
+// The wavefront schedule (launch_wavefront + wf_round of device_api.hip): rounds of k_wf_advance -> k_wf_regen -> trace A ->
 // k_wf_begin -> trace B -> k_wf_query -> trace C over an HBM-style path pool until every tile is done. All kernels run as SIMT
 // emulations (`trace` is kept in the signature: 0 = k_wf_trace_dyn, the only traversal kernel). Moving scenes run the ANIM = 1 kernels with
 // the per-slot transform cache.
-// n_chunks = 256-slot chunks of the pool (<= tile_count); lds_depth as in emu_wf_trace.
-int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t spp, uint64_t seed, float* rgbw,
-                         int trace, uint32_t n_chunks, uint32_t trace_blocks, uint32_t lds_depth, unsigned long long* stats_out) {
+// n_chunks = 256-slot chunks of the pool (<= tile_count); lds_depth as in emu_wf_trace. [smp_begin, smp_end): the samples of the spp-sample frame to
+// render, 0 / 0 = all of them.
+static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t spp, uint32_t smp_begin, uint32_t smp_end, uint64_t seed,
+                            float* rgbw, int trace, uint32_t n_chunks, uint32_t trace_blocks, uint32_t lds_depth, unsigned long long* stats_out) {
     EmuScene e;
     make_scene(f, e);
-    bool moving = f->camera.animated != 0;
-    for (uint32_t t_ = 0; t_ < f->n_textures; ++t_) moving = moving || f->textures[t_].n_frames >= 2u;   // animated_image needs ray.time (tray_scene_create)
+    const bool moving = scene_moves(f);
     uint32_t n_moving = 0;
-    for (uint32_t i = 0; i < f->n_instances; ++i) {
-        moving = moving || f->instances[i].animated != 0 || f->instances[i].emis_count >= 2;
-        if (f->instances[i].animated) ++n_moving;
-    }
+    for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].animated) ++n_moving;
     e.d.film_rows = film_rows_ok(f) ? 1u : 0u;
-    // launch_wavefront's rule: tiles are cut into slices of their samples while the pool has more chunks than work items (k_wf_advance)
-    uint32_t slice_shift = 0u;
-    while ((1u << (slice_shift + 1u)) <= 16u && ((uint64_t)tile_count << (slice_shift + 1u)) <= n_chunks && (spp >> (slice_shift + 1u)) >= 16u) ++slice_shift;
-    if (const char* sl = getenv("TRAYHIP_WF_SLICES")) { slice_shift = 0u; while ((2u << slice_shift) <= (uint32_t)std::max(1, atoi(sl)) && (2u << slice_shift) <= 16u && (spp >> (slice_shift + 1u)) >= 1u) ++slice_shift; }
+    tr_rules::whole_frame_range(spp, smp_begin, smp_end);
+    const uint32_t n_smp = tr_rules::range_samples(spp, smp_begin, smp_end);
+    const uint32_t slice_shift = tr_rules::wf_slice_shift(tile_count, n_chunks, n_smp, 0u);
     const uint32_t n_items = tile_count << slice_shift;
     n_chunks = std::max(1u, std::min(n_chunks, n_items));
     const uint32_t n_slots = n_chunks * TR_BLOCK, n_active = n_slots;
@@ -528,7 +505,7 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
         xf_cache.assign((size_t)n_moving * TR_XF_REC * n_slots, 0.0f);
         e.d.xf_cache = xf_cache.data(); e.d.moving_ids = moving_ids.data(); e.d.n_moving = n_moving; e.d.xf_stride = n_moving; e.d.xf_cache_lanes = n_slots; e.d.xf_aos = 1u;
     }
-    SparseXfTable table;   // TRAYHIP_EMU_XF_TABLE=1: the stage kernels index the frame's table by the path's time index (device_api.hip: xf_table_prepare's wavefront branch)
+    SparseXfTable table;   // TRAYHIP_EMU_XF_TABLE=1: the stage kernels index the frame's table by the path's time index (device_api.hip: launch_prepare's wavefront branch)
     if (moving && getenv("TRAYHIP_EMU_XF_TABLE") && atoi(getenv("TRAYHIP_EMU_XF_TABLE")) != 0) {
         if (!table.build(f, e.d.frame, moving_ids.data(), n_moving, tiles_xy, tile_count, spp, seed)) return -5;
         if (table.data) {
@@ -547,7 +524,7 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
     std::memset(stats.data(), 0, stats.size() * sizeof(DevStats));
     std::vector<uint2> tiles(tile_count);
     for (uint32_t i = 0; i < tile_count; ++i) tiles[i] = make_uint2(tiles_xy[2 * i], tiles_xy[2 * i + 1]);
-    const uint32_t kf = key_frame_host(seed, e.d.frame);
+    const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
     const uint32_t full = e.quad_words;
     if (lds_depth == 0 || lds_depth > full) lds_depth = full;
     trace_blocks = std::max(1u, std::min(trace_blocks, n_chunks));
@@ -561,7 +538,7 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
     std::vector<uint32_t> kind_queues((size_t)WF_MAT_KINDS * q_cap, 0u);
     uint32_t kinds_present = 0;
     for (const DevMaterial& dm : e.mats) kinds_present |= 1u << dm.mat_kind;
-    const uint64_t max_rounds = (uint64_t)((n_items + n_chunks - 1) / n_chunks) * (((uint64_t)spp + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * e.d.max_depth + 3) + 4) + 32;
+    const uint64_t max_rounds = (uint64_t)((n_items + n_chunks - 1) / n_chunks) * (((uint64_t)n_smp + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * e.d.max_depth + 3) + 4) + 32;
     int rc = 0;
     uint64_t rounds = 0;
     // ray binning before the traversal stages, as launch_wavefront sets it up (TRAYHIP_WF_BIN: bit 0 = stage A, bit 1 = stage B)
@@ -573,10 +550,10 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
     const WfBinGrid bin_grid = f->n_top_nodes ? wf_bin_grid(f->top_nodes[0].bmin, f->top_nodes[0].bmax) : WfBinGrid{};
     const uint32_t bin_blocks = (pool.seg_cap + WF_BIN_EPB - 1u) / WF_BIN_EPB * WF_SEGS;
 #define EMU_K(...) do { if (rc == 0) rc = launch_simt(__VA_ARGS__); } while (0)
-#define EMU_ROUND(A, F)                                                                                                                     \
+#define EMU_ROUND(A)                                                                                                                        \
     do {                                                                                                                                    \
         EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_advance<A>(e.d, pool, chunks.data(), bins.data(), tiles.data(), n_items, tile_count, 1u, spp, kf, rgbw, \
-                                                         counters, counters + 1, stats.data(), qa, qr, qctl, slice_shift); });                          \
+                                                         counters, counters + 1, stats.data(), qa, qr, qctl, slice_shift EMU_RANGE(smp_begin, smp_end)); }); \
         EMU_K(q_blocks, TR_BLOCK, [&] { k_wf_regen<A>(e.d, pool, chunks.data(), tiles.data(), tile_count, 1u, spp, kf, stats.data(), qr, qa, qctl, slice_shift); }); \
         if (WF_FOLD_C && (bin_stages & 1u)) { EMU_BIN(0, qa, qc, bin_ctl.data()); EMU_TRACE_STAGE(0, A, qc, qb); }   /* wf_round: the binned copy lies in the idle queue's buffer */ \
         else EMU_TRACE_STAGE(0, A, qa, qb);                                                                                                   \
@@ -591,7 +568,7 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
         EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_begin<A>(e.d, pool, n_active, stats.data(), qb, qctl, sorted ? kind_queues.data() : nullptr); }); \
         if (WF_FOLD_C && (bin_stages & 2u)) { EMU_BIN(1, qb, qa, bin_ctl.data() + 2u * WF_SEGS * WF_BINS); EMU_TRACE_STAGE(1, A, qa, qc); }     \
         else EMU_TRACE_STAGE(1, A, qb, qc);                                                                                                   \
-        if (sorted) {   /* wf_round of kernels.hip: one kind-pure shading launch per material kind of the scene */                        \
+        if (sorted) {   /* wf_round: one kind-pure                shading launch per material kind of the scene */                        \
             EMU_QUERY_KIND(A, TRAY_MAT_MATTE); EMU_QUERY_KIND(A, TRAY_MAT_PLASTIC); EMU_QUERY_KIND(A, TRAY_MAT_METAL); EMU_QUERY_KIND(A, TRAY_MAT_GLASS); \
             EMU_QUERY_KIND(A, TRAY_MAT_ROUGH_GLASS); EMU_QUERY_KIND(A, TRAY_MAT_SPECULAR_METAL); EMU_QUERY_KIND(A, TRAY_MAT_MERL);          \
         } else EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_query<A, FEAT_ALL | FEAT_TEX>(e.d, pool, n_active, WF_FOLD_C ? nullptr : qc, qctl, stats.data(), qa); });  \
@@ -611,19 +588,12 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
         EMU_K(bin_blocks, TR_BLOCK, [&] { k_wf_bin_hist<S>(pool, Q, qctl, CTL, bin_grid); });                                               \
         EMU_K(bin_blocks, TR_BLOCK, [&] { k_wf_bin_scatter<S>(pool, Q, OUT, qctl, CTL, bin_grid); });                                       \
     } while (0)
-#define EMU_ROUND_F(A)                                                                                                                      \
-    do {                                                                                                                                    \
-        if (feat == FEAT_NONE) EMU_ROUND(A, FEAT_NONE); else if (feat == FEAT_MERL) EMU_ROUND(A, FEAT_MERL);                                \
-        else if (feat == FEAT_SPEC) EMU_ROUND(A, FEAT_SPEC); else if (feat == (FEAT_MERL | FEAT_SPEC)) EMU_ROUND(A, FEAT_MERL | FEAT_SPEC);  \
-        else if (feat == (FEAT_ALL | FEAT_TEX)) EMU_ROUND(A, FEAT_ALL | FEAT_TEX); else EMU_ROUND(A, FEAT_ALL);                                                                                                        \
-    } while (0)
     std::memset(qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t));
     while (rc == 0 && counters[1] < n_items) {
         std::fill(bin_ctl.begin(), bin_ctl.end(), 0u);
-        if (moving) EMU_ROUND_F(1); else EMU_ROUND_F(0);
+        if (moving) EMU_ROUND(1); else EMU_ROUND(0);
         if (++rounds > max_rounds) rc = -5;   // "wavefront schedule did not terminate"
     }
-#undef EMU_ROUND_F
 #undef EMU_BIN
 #undef EMU_TRACE_STAGE
 #undef EMU_QUERY_KIND
@@ -636,6 +606,10 @@ int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
         stats_out[0] = st.samples; stats_out[1] = st.vertices; stats_out[2] = st.rays; stats_out[3] = rounds;
     }
     return rc;
+}
+int emu_render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t tile_count, uint32_t spp, uint64_t seed, float* rgbw,
+                         int trace, uint32_t n_chunks, uint32_t trace_blocks, uint32_t lds_depth, unsigned long long* stats_out) {
+    return render_wavefront(f, tiles_xy, tile_count, spp, 0u, 0u, seed, rgbw, trace, n_chunks, trace_blocks, lds_depth, stats_out);
 }
 
 uint32_t emu_wf_bin_cells(void) { return 1u << WF_BIN_CELL_BITS; }

@@ -135,7 +135,7 @@ TR_DEV uint32_t xf_cache_lane() { return blockIdx.x * blockDim.x + threadIdx.x; 
 // 1.9 GB per moving instance. The wavefront kernels index it directly: a path's `column` is its time index, nothing is evaluated or stored per
 // path (C5 stand-in, frame 64: 186 -> 213 Msamples/s). The tile kernel keeps its per-thread cache columns (coalesced reads in the flat instance
 // loop; gathered 112-byte records there measured only +3.5 % on moving_box) and FILLS them from the table instead of evaluating. The host builds
-// the table for launches of enough samples (kernels.hip: xf_table_prepare), the per-path evaluation serves the others.
+// the table for launches of enough samples (device_api.hip: launch_prepare), the per-path evaluation serves the others.
 #ifndef TR_XF_FILL_COOP   // the tile kernel's fill of its cache columns from the frame's table: 1 = dealt out to the whole wave (xf_cache_fill_wave), 0 = by the starting lanes
 #define TR_XF_FILL_COOP 1
 #endif

@@ -6,9 +6,11 @@
 #include <cmath>
 #define TR_INST_EXTERN   // explicit instantiation declarations of every kernel the launch sites below name
 #include "kernel_list.h"
+#include "kernel_select.h"   // (after the declarations: the selectors instantiate no kernel here)
 #include "kernel_ranges.h"
 #include "noise.h"
 #undef TR_INST_EXTERN
+#include "launch_rules.h"
 
 
 #ifndef WF_PIPES_MAX
@@ -194,9 +196,6 @@ static int upload(TrayDeviceScene* s, const char* key, bool unchanged, const T* 
 #define WF_SLOTS (128u << 20)
 #endif
 #define WF_POLL 16
-#ifndef WF_MAX_SLICES
-#define WF_MAX_SLICES 16u  // work items a tile's samples are cut into at most (k_wf_advance): the pool may hold that many chunks per tile
-#endif
 // one round of the wavefront schedule: advance -> regen -> trace A -> begin -> trace B -> query -> trace C (compacted ray queues, persistent
 // traversal with dynamic fetch, kind-pure shading over the material sort's queues; scenes with textured materials, whose lobes
 // exist per hit only, shade unsorted in the one instantiation that lowers them)
@@ -396,17 +395,13 @@ void tray_scene_destroy(TrayDeviceScene* s) {
 
 } // extern "C" (scene_build is internal)
 
-// the k_path_tiles instantiation launch_tiles runs for this scene (same selection as its PATH_TILES_F): what the occupancy is asked of
+// the k_path_tiles instantiation launch_tiles runs for this scene: what the occupancy is asked of
 static const void* tile_kernel(const TrayDeviceScene* s) {
-#define TK(A, F) (s->light_filter ? reinterpret_cast<const void*>(k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, true>) : reinterpret_cast<const void*>(k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, false>))
-#define TK_F(A) (s->feat == FEAT_NONE ? TK(A, FEAT_NONE) : s->feat == FEAT_MERL ? TK(A, FEAT_MERL) : s->feat == FEAT_SPEC ? TK(A, FEAT_SPEC) \
-                 : s->feat == (FEAT_MERL | FEAT_SPEC) ? TK(A, FEAT_MERL | FEAT_SPEC) : s->feat == (FEAT_ALL | FEAT_TEX) ? TK(A, FEAT_ALL | FEAT_TEX) : TK(A, FEAT_ALL))
-    if (s->dev.integrator == TRAY_INTEGRATOR_WHITTED)
-        return s->animated ? reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>)
-                           : reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>);
-    return s->animated ? TK_F(1) : TK_F(0);
-#undef TK_F
-#undef TK
+    const void* k = nullptr;
+    const auto take = [&](auto kernel) { k = reinterpret_cast<const void*>(kernel); };
+    const bool whitted = s->dev.integrator == TRAY_INTEGRATOR_WHITTED;
+    if (s->animated) select_path_tiles<1>(s->feat, whitted, s->light_filter, take); else select_path_tiles<0>(s->feat, whitted, s->light_filter, take);
+    return k;
 }
 
 // bytes of a per-path transform cache of `lanes` paths (records of the wavefront schedule / rows of columns of the tile kernel: dev_anim.h)
@@ -967,14 +962,8 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
 static int launch_wavefront(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                             uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     const WfBuffers& w = s->lb.wf;
-    const uint32_t n = smp_end ? smp_end - smp_begin : spp;   // samples per pixel this launch renders: the rules below cut them (a slice is never empty: 2^slice_shift <= n)
-    // tiles are cut into slices of their samples while the pool has at least as many chunks as the launch then has work items
-    // (k_wf_advance; a slice costs its own film resolve: at 8 M slots and 32 400 tiles halving them measured 124 against 132 Msamples/s); a
-    // slice keeps at least 16 samples per pixel (TRAYHIP_WF_SLICES overrides: 1, 2, 4)
-    uint32_t slice_shift = 0u;
-    while ((1u << (slice_shift + 1u)) <= WF_MAX_SLICES && ((uint64_t)tile_count << (slice_shift + 1u)) <= w.n_chunks && (n >> (slice_shift + 1u)) >= 16u) ++slice_shift;   // (cut while the items still fit the chunks: one item per chunk is the optimum)
-    if (s->wf_req_slices) { slice_shift = 0u; while ((2u << slice_shift) <= s->wf_req_slices && (2u << slice_shift) <= WF_MAX_SLICES && (n >> (slice_shift + 1u)) >= 1u) ++slice_shift; }   // tray_scene_set_wavefront
-    if (const char* e = getenv("TRAYHIP_WF_SLICES")) { slice_shift = 0u; while ((2u << slice_shift) <= (uint32_t)std::max(1, atoi(e)) && (2u << slice_shift) <= WF_MAX_SLICES && (n >> (slice_shift + 1u)) >= 1u) ++slice_shift; }
+    const uint32_t n = tr_rules::range_samples(spp, smp_begin, smp_end);
+    const uint32_t slice_shift = tr_rules::wf_slice_shift(tile_count, w.n_chunks, n, s->wf_req_slices);
     tile_count <<= slice_shift;   // from here on: work items
     const uint32_t n_chunks = std::min(w.n_chunks, tile_count);
     HIP_CHECK(hipMemsetAsync(w.d_wf_counters, 0, 2 * sizeof(uint32_t), stream));
@@ -1078,25 +1067,17 @@ int tray_scene_set_sampler(TrayDeviceScene* s, uint32_t kind, uint32_t min_spp, 
 int tray_render_tiles_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint64_t seed,
                              float* rgbw_dev, void* stream_) {
     if (!s || !rgbw_dev) { set_error("tray_render_tiles_device: null argument"); return TRAY_E_INVALID; }
-    if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // BlockQueue::new ignores `start` when count == 0 (block_queue.rs:39-41), like tray_block_queue
-    if (tile_start > s->n_tiles) tile_start = s->n_tiles;                       // skip(start).take(count)
-    if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
-    return launch_tiles(s, s->d_tiles + tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_);
+    tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
+    const tr_rules::TileWork w = tr_rules::whole_queue(tile_count);
+    return launch_tiles(s, s->d_tiles + tile_start, w.work, w.chunk, w.chunk_stride, spp, seed, rgbw_dev, stream_);
 }
 
 int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles, uint32_t spp, uint64_t seed,
                              float* rgbw_dev, void* stream_) {
     if (!s || !rgbw_dev) { set_error("tray_render_shard_device: null argument"); return TRAY_E_INVALID; }
     if (n_shards == 0 || shard >= n_shards || chunk_tiles == 0) { set_error("tray_render_shard_device: bad shard / chunk arguments"); return TRAY_E_INVALID; }
-    // chunks c = shard, shard + n_shards, ... of chunk_tiles tiles each; the last chunk may be short
-    uint32_t n_chunks = (s->n_tiles + chunk_tiles - 1) / chunk_tiles;
-    uint32_t my_chunks = shard < n_chunks ? (n_chunks - shard + n_shards - 1) / n_shards : 0;
-    if (my_chunks == 0) return launch_tiles(s, s->d_tiles, 0, 1, 1, spp, seed, rgbw_dev, stream_);
-    uint32_t last_chunk = shard + (my_chunks - 1) * n_shards;
-    uint32_t tail = s->n_tiles - last_chunk * chunk_tiles;   // tiles in my last chunk
-    if (tail > chunk_tiles) tail = chunk_tiles;
-    uint32_t work = (my_chunks - 1) * chunk_tiles + tail;
-    return launch_tiles(s, s->d_tiles + shard * chunk_tiles, work, chunk_tiles, n_shards, spp, seed, rgbw_dev, stream_);
+    const tr_rules::TileWork w = tr_rules::shard_work(s->n_tiles, shard, n_shards, chunk_tiles);
+    return launch_tiles(s, s->d_tiles + w.first, w.work, w.chunk, w.chunk_stride, spp, seed, rgbw_dev, stream_);
 }
 
 int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint32_t sample_begin, uint32_t sample_end,
@@ -1105,10 +1086,9 @@ int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t
     if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID; }
     if (sample_begin >= sample_end || sample_end > spp) { set_error("tray_render_samples_device: the range must satisfy sample_begin < sample_end <= spp"); return TRAY_E_INVALID; }
     if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error("tray_render_samples_device: sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
-    if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // as tray_render_tiles_device
-    if (tile_start > s->n_tiles) tile_start = s->n_tiles;
-    if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
-    return launch_tiles(s, s->d_tiles + tile_start, tile_count, tile_count ? tile_count : 1, 1, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
+    tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
+    const tr_rules::TileWork w = tr_rules::whole_queue(tile_count);
+    return launch_tiles(s, s->d_tiles + tile_start, w.work, w.chunk, w.chunk_stride, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
 }
 
 // tray_render_noise_target_device's rounds over queue[0, tile_count) (include/trayhip.h), with s->accumulate set: round r renders [a, b) --
@@ -1152,9 +1132,7 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
     if (even_dev == odd_dev) { set_error("tray_render_noise_target_device: the even and odd films must be different buffers"); return TRAY_E_INVALID; }
     if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error("tray_render_noise_target_device: sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
     if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
-    if (tile_count == 0) { tile_start = 0; tile_count = s->n_tiles; }          // as tray_render_tiles_device
-    if (tile_start > s->n_tiles) tile_start = s->n_tiles;
-    if (tile_count > s->n_tiles - tile_start) tile_count = s->n_tiles - tile_start;
+    tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_CHECK(hipSetDevice(s->device));
     s->timing_valid = false;
@@ -1204,14 +1182,7 @@ static int launch_sampler(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_
                           uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     SamplerPass sp{};
     sp.kind = s->sampler_kind; sp.min_spp = s->smp_min; sp.max_spp = s->smp_max;
-    uint32_t rounds = 1;
-    if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY) {   // (scenes with an AnimatedMesh: LowDiscrepancy::get_samples hands out all spp samples of a pixel at once, ld.rs:33-52)
-        sp.min_spp = sp.max_spp = spp; sp.step = 1u; sp.lum_cap = 0u;
-    } else if (sp.kind == TRAY_SAMPLER_ADAPTIVE) {
-        sp.step = tray_adaptive_step(sp.min_spp, sp.max_spp);
-        while (sp.min_spp + (rounds - 1u) * sp.step < sp.max_spp) ++rounds;     // get_samples until samples_taken >= max_spp (adaptive.rs:136)
-        sp.lum_cap = sp.min_spp + (rounds - 1u) * sp.step;
-    } else { sp.min_spp = sp.max_spp = 1u; sp.step = 1u; sp.lum_cap = 0u; }
+    const uint32_t rounds = tr_rules::sampler_plan(sp, spp);
     // tiles per batch: the per-pixel state within 256 MB and the largest round within 2^28 threads
     const size_t px_bytes = 8u + 4u * (size_t)sp.lum_cap;
     const uint32_t widest = std::max(sp.min_spp, sp.step);
@@ -1232,26 +1203,17 @@ static int launch_sampler(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_
         const uint32_t n_items = std::min(batch, tile_count - item0), n_px = n_items * 64u;
         if (sp.kind == TRAY_SAMPLER_ADAPTIVE) HIP_CHECK(hipMemsetAsync(s->d_smp, 0, (size_t)batch * 64u * 8u, stream));   // states and averages
         for (uint32_t j = 0; j < rounds; ++j) {
-            sp.pass = j;
-            sp.count = sp.kind == TRAY_SAMPLER_ADAPTIVE ? (j == 0u ? sp.min_spp : sp.step) : sp.min_spp;   // (Uniform: 1, LowDiscrepancy: spp)
-            if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY && smp_end) sp.count = smp_end - smp_begin;   // (a range: its samples of the spp-sample frame, from smp_begin on)
-            sp.taken = sp.kind == TRAY_SAMPLER_ADAPTIVE ? sp.min_spp + j * sp.step : 0u;
-            sp.before = j == 0u ? 0u : sp.min_spp + (j - 1u) * sp.step;
-            // (k_sampler_pass: a workgroup owns a group of consecutive tiles -- enough of them for ~4096 (pixel, sample) pairs of the round, 16 at most: a
-            // 32 x 32 pixel square of the Z-order queue -- and hands the pairs to its lanes as their paths end)
-            const uint32_t per_tile = 64u * sp.count;
-            uint32_t group = std::max(1u, std::min<uint32_t>(SP_GROUP_MAX, 4096u / per_tile));
-            if (const char* ge = getenv("TRAYHIP_SAMPLER_GROUP")) group = (uint32_t)std::max(1, std::min(SP_GROUP_MAX, atoi(ge)));   // (measurement)
+            tr_rules::sampler_round(sp, j, smp_end ? smp_end - smp_begin : 0u);
+            const uint32_t group = tr_rules::sampler_group(sp.count, SP_GROUP_MAX);
             const dim3 grid((n_items + group - 1u) / group), block(TR_BLOCK);
-#define SAMPLER_PASS(A, F) hipLaunchKernelGGL((k_sampler_pass<A, F>), grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group)
-            const bool lean = s->feat == FEAT_NONE && s->dev.integrator != TRAY_INTEGRATOR_WHITTED;   // (no optional lobe, no texture: the small instantiation)
+            const int anim = s->deforming ? 3 : s->animated ? 2 : 0;
+            const bool lean = sampler_lean(s->feat, s->dev.integrator);
             if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY && smp_end)
-                tr_ranges::sampler_pass(s->deforming ? 3 : s->animated ? 2 : 0, lean, grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk,
-                                        chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group, smp_begin);
-            else if (s->deforming) { if (lean) SAMPLER_PASS(3, FEAT_NONE); else SAMPLER_PASS(3, FEAT_ALL | FEAT_TEX); }
-            else if (s->animated) { if (lean) SAMPLER_PASS(2, FEAT_NONE); else SAMPLER_PASS(2, FEAT_ALL | FEAT_TEX); }
-            else { if (lean) SAMPLER_PASS(0, FEAT_NONE); else SAMPLER_PASS(0, FEAT_ALL | FEAT_TEX); }
-#undef SAMPLER_PASS
+                tr_ranges::sampler_pass(anim, lean, grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum,
+                                        rgbw_dev, s->d_stats, group, smp_begin);
+            else select_sampler_pass(anim, lean, [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum, rgbw_dev, s->d_stats, group);
+            });
             ++launches;
             if (sp.kind == TRAY_SAMPLER_ADAPTIVE) {
                 hipLaunchKernelGGL(k_sampler_decide, dim3((n_px + TR_BLOCK - 1) / TR_BLOCK), block, 0, stream, n_px, sp, px_state, px_avg, px_lum);
@@ -1405,13 +1367,9 @@ static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_co
         HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));
         HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
     }
-    // key_frame on the host (same mixing as the device function)
-    auto mix = [](uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; };
-    uint32_t kf = mix((uint32_t)seed + 0x9E3779B9u);
-    kf = mix(kf ^ (uint32_t)(seed >> 32));
-    kf = mix(kf + s->dev.frame);
-    if (smp_begin == 0u && smp_end == spp) smp_end = 0u;   // (the whole frame as a range: the whole-frame launch)
-    const uint32_t n_smp = smp_end ? smp_end - smp_begin : spp;   // samples per pixel of this launch
+    const uint32_t kf = tr_rules::frame_key(seed, s->dev.frame);
+    tr_rules::whole_frame_range(spp, smp_begin, smp_end);
+    const uint32_t n_smp = tr_rules::range_samples(spp, smp_begin, smp_end);
     if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
     s->last_was_wavefront = false;
     const bool had_pool = s->lb.wf.ready;
@@ -1430,22 +1388,7 @@ static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_co
                                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
         return rc;
     }
-    // Items per tile (k_path_tiles: progressive slices, level-major: the launch ends with its smallest items). A slice costs its own film resolve and
-    // flush and keeps >= 64 samples per pixel (>= 256 in a launch with many tiles per workgroup). Measured (profiles/r06_tile_slices_progressive_ab.txt, items per tile 1 / 2 / 3 / 4 / 5): the whole
-    // dragon frame 718.5 / 740.6 / 750.3 / 752.7 / 755.1 Msamples/s (tiles that show the mesh cost several times a wall tile: with whole tiles the last
-    // round of the 768 workgroups is one such tile), the whole cornell_box frame 1160.9 / 1163.5 / 1163.6 / 1159.9 / 1154.3; a GPU's eighth of the
-    // frame (4050 tiles, slowest of the eight shards against an eighth of the whole frame): dragon 0.449 / 0.632 / 0.784 / 0.862 / 0.872,
-    // cornell_box 0.895 / 0.942 / 0.960 / 0.971 / 0.975. So: three items per tile for a launch with many tiles per workgroup, up to five for a small one.
-    // TRAYHIP_TILE_SLICES=<items per tile> overrides. A sample range is cut by the same rules over its n_smp samples (k_path_tiles: any n_smp >= 1).
-    uint32_t levels = 1u;
-    {
-        // (a launch with many tiles per workgroup keeps >= 256 samples per slice: at 256 spp three items per tile cost cornell_box 2.8 %, 1114 against 1146
-        // Msamples/s, profiles/r06_c2_kept_gate_distance_ab.txt -- the resolves outweigh a tail that is 1 / 42 of the launch there)
-        const bool small = tile_count < 12u * (uint32_t)s->n_blocks;
-        const uint32_t most = small ? 5u : 3u, least = small ? 64u : 256u;
-        while (levels < most && (n_smp >> levels) >= least) ++levels;   // (the last two slices are spp >> (levels - 1) samples each)
-    }
-    if (const char* e = getenv("TRAYHIP_TILE_SLICES")) { levels = 1u; const uint32_t want = (uint32_t)std::max(1, atoi(e)); while (levels < want && (n_smp >> levels) >= 1u) ++levels; }
+    const uint32_t levels = tr_rules::tile_levels(tile_count, (uint32_t)s->n_blocks, n_smp);   // items per tile: progressive slices
     int blocks = (int)std::min<uint64_t>((uint64_t)s->n_blocks, (uint64_t)tile_count * levels);
 #ifdef TR_SAMPLE_DUMP
     void* dump_buf = nullptr;
@@ -1457,23 +1400,14 @@ static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_co
     s->launch_dev.sample_dump = static_cast<float4*>(dump_buf);
 #endif
     if (!s->accumulate) HIP_CHECK(hipEventRecord(s->ev0, stream));
-#define PATH_TILES_L(A, F, L) hipLaunchKernelGGL((k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, L>), dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, tiles, \
-                                                 tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats)
-#define PATH_TILES(A, F) do { if (s->light_filter) PATH_TILES_L(A, F, true); else PATH_TILES_L(A, F, false); } while (0)
-#define PATH_TILES_F(A) do { if (s->feat == FEAT_NONE) PATH_TILES(A, FEAT_NONE); else if (s->feat == FEAT_MERL) PATH_TILES(A, FEAT_MERL); \
-                             else if (s->feat == FEAT_SPEC) PATH_TILES(A, FEAT_SPEC); else if (s->feat == (FEAT_MERL | FEAT_SPEC)) PATH_TILES(A, FEAT_MERL | FEAT_SPEC); \
-                             else if (s->feat == (FEAT_ALL | FEAT_TEX)) PATH_TILES(A, FEAT_ALL | FEAT_TEX); else PATH_TILES(A, FEAT_ALL); } while (0)
-#define WHITTED_TILES(A) hipLaunchKernelGGL((k_path_tiles<A, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>), dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, \
-                                             tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats)
-    if (smp_end) tr_ranges::path_tiles(s->animated ? 1 : 0, s->feat, s->dev.integrator == TRAY_INTEGRATOR_WHITTED, s->light_filter, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream,
+    const bool whitted = s->dev.integrator == TRAY_INTEGRATOR_WHITTED;
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats);
+    };
+    if (smp_end) tr_ranges::path_tiles(s->animated ? 1 : 0, s->feat, whitted, s->light_filter, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream,
                                        s->launch_dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats, smp_begin, smp_end);
-    else if (s->dev.integrator == TRAY_INTEGRATOR_WHITTED) { if (s->animated) WHITTED_TILES(1); else WHITTED_TILES(0); }
-    else if (s->animated) PATH_TILES_F(1);
-    else PATH_TILES_F(0);
-#undef WHITTED_TILES
-#undef PATH_TILES_F
-#undef PATH_TILES
-#undef PATH_TILES_L
+    else if (s->animated) select_path_tiles<1>(s->feat, whitted, s->light_filter, launch);
+    else select_path_tiles<0>(s->feat, whitted, s->light_filter, launch);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(s->ev1, stream));
     s->timing_valid = true;

@@ -9,39 +9,28 @@
 #define TR_SAMPLE_RANGES
 #include "kernels.hip"
 #include "kernel_ranges.h"
+#include "kernel_select.h"
 
 namespace tr_ranges {
 
-#if TR_RANGE_GROUP == 0 || TR_RANGE_GROUP == 1
-#define RANGE_TILES_L(A, F, L) hipLaunchKernelGGL((k_path_tiles<A, F, TRAY_INTEGRATOR_PATH, L>), grid, block, lds, stream, dev, tiles, tile_count, chunk, chunk_stride, \
-                                                  spp, kf, levels, rgbw, counter, stats, smp_begin, smp_end)
-#define RANGE_TILES(A, F) do { if (light_filter) RANGE_TILES_L(A, F, true); else RANGE_TILES_L(A, F, false); } while (0)
-#define RANGE_TILES_F(A) do { if (whitted) hipLaunchKernelGGL((k_path_tiles<A, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>), grid, block, lds, stream, dev, tiles, \
-                                                              tile_count, chunk, chunk_stride, spp, kf, levels, rgbw, counter, stats, smp_begin, smp_end); \
-                              else if (feat == FEAT_NONE) RANGE_TILES(A, FEAT_NONE); else if (feat == FEAT_MERL) RANGE_TILES(A, FEAT_MERL); \
-                              else if (feat == FEAT_SPEC) RANGE_TILES(A, FEAT_SPEC); else if (feat == (FEAT_MERL | FEAT_SPEC)) RANGE_TILES(A, FEAT_MERL | FEAT_SPEC); \
-                              else if (feat == (FEAT_ALL | FEAT_TEX)) RANGE_TILES(A, FEAT_ALL | FEAT_TEX); else RANGE_TILES(A, FEAT_ALL); } while (0)
 // (group 0 defines path_tiles and launches the static instantiations; the moving ones are group 1's, reached through path_tiles_moving)
 #if TR_RANGE_GROUP == 1
 void path_tiles_moving(int feat, bool whitted, bool light_filter, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const tr::DevScene& dev,
                        const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride, uint32_t spp, uint32_t kf, uint32_t levels, float* rgbw,
                        uint32_t* counter, DevStats* stats, uint32_t smp_begin, uint32_t smp_end) {
-    RANGE_TILES_F(1);
+    select_path_tiles<1>(feat, whitted, light_filter, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw, counter, stats, smp_begin, smp_end);
+    });
 }
-#else
-void path_tiles_moving(int feat, bool whitted, bool light_filter, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const tr::DevScene& dev,
-                       const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride, uint32_t spp, uint32_t kf, uint32_t levels, float* rgbw,
-                       uint32_t* counter, DevStats* stats, uint32_t smp_begin, uint32_t smp_end);
+#elif TR_RANGE_GROUP == 0
 void path_tiles(int anim, int feat, bool whitted, bool light_filter, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const tr::DevScene& dev,
                 const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride, uint32_t spp, uint32_t kf, uint32_t levels, float* rgbw,
                 uint32_t* counter, DevStats* stats, uint32_t smp_begin, uint32_t smp_end) {
     if (anim) { path_tiles_moving(feat, whitted, light_filter, grid, block, lds, stream, dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw, counter, stats, smp_begin, smp_end); return; }
-    RANGE_TILES_F(0);
+    select_path_tiles<0>(feat, whitted, light_filter, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw, counter, stats, smp_begin, smp_end);
+    });
 }
-#endif
-#undef RANGE_TILES_F
-#undef RANGE_TILES
-#undef RANGE_TILES_L
 #endif
 
 #if TR_RANGE_GROUP == 2
@@ -58,12 +47,9 @@ void wf_advance(int anim, dim3 grid, dim3 block, hipStream_t stream, const tr::D
 void sampler_pass(int anim, bool lean, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const tr::DevScene& dev, const uint2* tiles,
                   uint32_t item0, uint32_t n_items, uint32_t chunk, uint32_t chunk_stride, uint32_t kf, const SamplerPass& sp,
                   const uint32_t* px_state, float* px_lum, float* rgbw, DevStats* stats, uint32_t group, uint32_t smp_first) {
-#define RANGE_PASS(A, F) hipLaunchKernelGGL((k_sampler_pass<A, F>), grid, block, lds, stream, dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, \
-                                            px_lum, rgbw, stats, group, smp_first)
-    if (anim == 3) { if (lean) RANGE_PASS(3, FEAT_NONE); else RANGE_PASS(3, FEAT_ALL | FEAT_TEX); }
-    else if (anim == 2) { if (lean) RANGE_PASS(2, FEAT_NONE); else RANGE_PASS(2, FEAT_ALL | FEAT_TEX); }
-    else { if (lean) RANGE_PASS(0, FEAT_NONE); else RANGE_PASS(0, FEAT_ALL | FEAT_TEX); }
-#undef RANGE_PASS
+    select_sampler_pass(anim, lean, [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum, rgbw, stats, group, smp_first);
+    });
 }
 #endif
 

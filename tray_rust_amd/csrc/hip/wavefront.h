@@ -81,7 +81,7 @@ struct WfPool {
     float* __restrict__ data;   // F_COUNT * n_slots dwords
     uint32_t n_slots;
     uint32_t seg_cap;           // entries per segment of every queue (wf_seg_cap(chunks of the pool)); a queue holds WF_SEGS * seg_cap
-    uint32_t first = 0u;        // a view's first slot (kernels.hip: WfView): slot i of the view is slot first + i of the pool
+    uint32_t first = 0u;        // a view's first slot (device_api.hip: WfView): slot i of the view is slot first + i of the pool
 };
 struct WfChunk { uint32_t tile, done, next_pair; };   // tile: index into the work list, WF_TILE_NEED or WF_TILE_IDLE; done: finished samples of the
                                                        // tile; next_pair: first (pixel, sample) pair of the tile not handed to a slot yet

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../../include/trayhip.h"
+#include "../hip/launch_rules.h"
 
 namespace trayh {
 
@@ -83,16 +84,8 @@ int tray_shard_tiles(uint32_t n_tiles, uint32_t shard, uint32_t n_shards, uint32
     return TRAY_OK;
 }
 
-uint32_t tray_round_spp(uint32_t spp) {   // ld.rs:22-25 (usize::next_power_of_two; 0 -> 1)
-    uint32_t p = 1;
-    while (p < spp && p < 0x80000000u) p <<= 1;
-    return p;
-}
-
-uint32_t tray_adaptive_step(uint32_t min_spp, uint32_t max_spp) {   // adaptive.rs:36-48
-    const uint32_t lo = tray_round_spp(min_spp), hi = tray_round_spp(max_spp);
-    return tray_round_spp(hi > lo ? (hi - lo) / 5u : 0u);
-}
+uint32_t tray_round_spp(uint32_t spp) { return tr_rules::round_spp(spp); }
+uint32_t tray_adaptive_step(uint32_t min_spp, uint32_t max_spp) { return tr_rules::adaptive_step(min_spp, max_spp); }
 
 int tray_resolve_srgb8(const float* rgbw, uint32_t width, uint32_t height, uint8_t* rgb8) {   // render_target.rs:185-210, color.rs:36-71
     if (!rgbw || !rgb8) { set_error("tray_resolve_srgb8: null argument"); return TRAY_E_INVALID; }

@@ -381,6 +381,37 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
                                     float threshold, uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples,
                                     float* tile_error, void* stream);
 
+/* Denoise a frame rendered as two half films (tray_render_noise_target_device's even / odd, or two sample ranges of equal size from
+ * tray_render_samples_device): dual-buffer non-local means (Rousselle, Knaus, Zwicker 2012). The difference of the halves estimates the noise
+ * per pixel, and each half is filtered with weights computed from the OTHER half, so that the noise does not pick its own weights. A function
+ * of two films: no scene handle. All arithmetic in f32, unfused; eps = 1e-7; sums over image positions skip positions outside the image.
+ * - Resolve. With E / O the pixel p of even_dev / odd_dev (RGBW, get_renderf32 layout): valid(p) = E.w > 0 and O.w > 0 and every component of
+ *   E and O is finite; a(p) = E.rgb / E.w, b(p) = O.rgb / O.w where valid, else 0.
+ * - Noise estimate. v_c(p) = (a_c - b_c)^2 / 2 per channel c (the variance of one half, estimated from the two); V_c(p) = the mean of v_c over
+ *   the valid pixels of the 3 x 3 box around p (0 if there is none). The halves of one low-discrepancy sequence are not independent; the
+ *   estimate is used as it is.
+ * - Distance of p and q = p + o, o in [-radius, radius]^2, in buffer x (a or b): with N(p, q) = the patch offsets n in [-patch, patch]^2 for
+ *   which p + n and q + n are both inside the image and valid,
+ *     t(p', q') = sum_c ((x_c(p') - x_c(q'))^2 - (V_c(p') + min(V_c(p'), V_c(q')))) / (eps + k^2 (V_c(p') + V_c(q'))),
+ *     d2_x(p, q) = sum_{n in N} t(p + n, q + n) / (3 |N|).
+ * - Weight. w_x(p, q) = exp(-max(0, d2_x(p, q))) if q is inside the image, valid and |N| > 0, else 0.
+ * - Cross filtering. A(p) = sum_q w_b(p, q) a(q) / sum_q w_b(p, q), B(p) likewise with w_a and b; a quotient whose denominator is 0 is 0.
+ *   out(p) = ((A + B) / 2, 1): an RGBW pixel of weight 1, which tray_resolve_srgb8 resolves like any film.
+ * - Missing pixels. An invalid p (the border pixels of a noise-target film whose weight ended <= 0, above) is left out of every patch,
+ *   contributes to nobody, and receives the weighted mean of its window like any pixel: the filter fills it from its neighbourhood.
+ * - Every output channel lies between the minimum and the maximum of that channel of a and b over the valid pixels of the pixel's window, up
+ *   to rounding. The order of the sums is the implementation's (a patch is summed separably); no atomics: the same bits in every run.
+ * tray_denoise_scratch_bytes: the bytes of device scratch tray_denoise_device needs for a width x height film (0 if width or height is 0).
+ * tray_denoise_device: out_dev = the filter of even_dev / odd_dev, in three kernel launches on `stream`, asynchronous, on the current device
+ * (tray_init). Returns TRAY_E_INVALID unless width, height >= 1, 1 <= radius <= 10, patch <= 3, k > 0 and finite, no pointer is null, out_dev
+ * differs from both films and the films from each other, and all four buffers are 16-byte aligned (hipMalloc's are). */
+#define TRAY_DENOISE_RADIUS 7
+#define TRAY_DENOISE_PATCH 3
+#define TRAY_DENOISE_K 0.45f
+uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                        float* out_dev, void* scratch_dev, void* stream);
+
 /* Host-side enumeration of the Morton-queue indices tray_render_shard_device renders for `shard`
  * (same mapping; lets callers and tests reason about the partition without a GPU). */
 int tray_shard_tiles(uint32_t n_tiles, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles,

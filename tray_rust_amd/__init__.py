@@ -311,6 +311,76 @@ class Hip:
             print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
         return samples, error
 
+    def _denoise_device(self, even, odd, radius, patch, k):
+        """tray_denoise_device of two (h, w, 4) float32 tensors of this device on the current stream; returns the output tensor"""
+        import torch
+        h, w = int(even.shape[0]), int(even.shape[1])
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(even)
+            scratch = torch.empty(max(int(lib().tray_denoise_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=even.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_device(w, h, C.c_void_p(even.data_ptr()), C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k),
+                                            C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return out
+
+    def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+        """The dual-buffer NL-means filter of include/trayhip.h (tray_denoise_device) of two half films, e.g. the even and odd film of a
+        noise-target render: two (h, w, 4) float32 RGBW arrays -- numpy arrays or torch tensors on this device -- in, the same kind out: an RGBW
+        film of weight 1. Pixels of weight <= 0 or with a non-finite component count as missing and are filled from their neighbourhood."""
+        import torch
+        as_numpy = isinstance(even, np.ndarray)
+        if as_numpy != isinstance(odd, np.ndarray):
+            raise TypeError("denoise: even and odd must both be numpy arrays or both be torch tensors")
+        dev = f"cuda:{self.device}"
+        if as_numpy:
+            e, o = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) for x in (even, odd))
+        else:
+            if even.device != torch.device(dev) or odd.device != torch.device(dev):
+                raise ValueError(f"denoise: the films must live on {dev}")
+            e, o = (x.to(torch.float32).contiguous() for x in (even, odd))
+            if o.data_ptr() == e.data_ptr():
+                o = o.clone()
+        if e.dim() != 3 or e.shape[2] != 4 or e.shape != o.shape:
+            raise ValueError("denoise: even and odd must be two (h, w, 4) films of one size")
+        out = self._denoise_device(e, o, radius, patch, k)
+        return out.cpu().numpy() if as_numpy else out
+
+    def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
+                        k=_lib.TRAY_DENOISE_K):
+        """config.select_blocks of the frame rendered as two half films and denoised on the device (tray_denoise_device); the RGBW output (weight 1)
+        is added into rt. With `threshold` the films are the even / odd film of tray_render_noise_target_device (see render_noise_target) and
+        (tile_samples, tile_error) is returned; without it they are the sample ranges [0, spp / 2) and [spp / 2, spp) of the
+        round_spp(config.spp)-sample frame (spp >= 2) and None is returned. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        import torch
+        dev = scene.device_scene(config.current_frame, self.device)
+        spp = self._select_sampler(dev, config.spp)
+        start, count = (int(v) for v in config.select_blocks)
+        w, h = rt.dimensions()
+        result = None
+        with torch.cuda.device(self.device):
+            even = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+            odd = torch.zeros_like(even)
+            stream = torch.cuda.current_stream().cuda_stream
+            if threshold is None:
+                if spp < 2:
+                    raise ValueError("render_denoised: two half films need spp >= 2")
+                for film, rng in ((even, (0, spp // 2)), (odd, (spp // 2, spp))):
+                    self.render_samples_device(scene, config.current_frame, (start, count), spp, rng, film.data_ptr(), stream or None)
+            else:
+                n = len(BlockQueue((w, h), (8, 8), (start, count)).blocks)
+                samples, error = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+                check(lib().tray_render_noise_target_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
+                                                            C.c_void_p(odd.data_ptr()), samples.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                            error.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(stream) if stream else None))
+                result = (samples, error)
+            t = _lib.TrayKernelTiming()
+            if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:   # (the last render call's: the whole noise-target call, or the second range)
+                self.last_timing = t
+            rt.add_pixels(self._denoise_device(even, odd, radius, patch, k).cpu().numpy())
+        return result
+
     def render_shard_device(self, scene, frame, shard, n_shards, spp, rgbw_ptr, chunk_tiles=16, stream=None):
         """One rank's share of a frame (round-robin chunks of the Morton queue); merge = sum over ranks."""
         dev = scene.device_scene(frame, self.device)

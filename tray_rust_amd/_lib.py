@@ -13,6 +13,7 @@ INST_RECEIVER, INST_AREA_EMITTER, INST_POINT_EMITTER = 0, 1, 2
 MAT_MATTE, MAT_PLASTIC, MAT_METAL, MAT_GLASS, MAT_ROUGH_GLASS, MAT_SPECULAR_METAL, MAT_MERL = range(7)
 FILTER_TABLE_SIZE = 16
 TRAY_PARTITION_TILES, TRAY_PARTITION_SAMPLES = 0, 1
+TRAY_DENOISE_RADIUS, TRAY_DENOISE_PATCH, TRAY_DENOISE_K = 7, 3, 0.45   # tray_denoise_device's defaults
 
 
 class TrayError(RuntimeError):
@@ -181,6 +182,8 @@ SYMBOLS = {
     "tray_render_samples_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "tray_render_noise_target_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint64, C.c_void_p,
                                                   C.c_void_p, _P(C.c_uint32), _P(C.c_float), C.c_void_p]),
+    "tray_denoise_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tray_multi_set_partition": (C.c_int, [C.c_void_p, C.c_int]),
     "tray_multi_shard_samples": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "tray_shard_tiles": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),

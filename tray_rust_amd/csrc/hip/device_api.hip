@@ -9,6 +9,7 @@
 #include "kernel_select.h"   // (after the declarations: the selectors instantiate no kernel here)
 #include "kernel_ranges.h"
 #include "noise.h"
+#include "denoise.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 
@@ -1164,6 +1165,27 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
     HIP_CHECK(hipStreamSynchronize(stream));
     s->launches = launches;
     s->timing_valid = true;
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height) { return tr_denoise::scratch_bytes(width, height); }
+
+int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                        float* out_dev, void* scratch_dev, void* stream_) {
+    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error("tray_denoise_device: null argument"); return TRAY_E_INVALID; }
+    if (width == 0u || height == 0u) { set_error("tray_denoise_device: width and height must be >= 1"); return TRAY_E_INVALID; }
+    if (radius < 1u || radius > 10u || patch > 3u) { set_error("tray_denoise_device: 1 <= radius <= 10 and patch <= 3 are required"); return TRAY_E_INVALID; }
+    if (!(k > 0.0f) || !std::isfinite(k)) { set_error("tray_denoise_device: k must be > 0 and finite"); return TRAY_E_INVALID; }
+    if (even_dev == odd_dev || out_dev == even_dev || out_dev == odd_dev) {
+        set_error("tray_denoise_device: the two films and the output must be three different buffers"); return TRAY_E_INVALID;
+    }
+    if ((reinterpret_cast<uintptr_t>(even_dev) | reinterpret_cast<uintptr_t>(odd_dev) | reinterpret_cast<uintptr_t>(out_dev) |
+         reinterpret_cast<uintptr_t>(scratch_dev)) & 15u) {
+        set_error("tray_denoise_device: the films, the output and the scratch buffer must be 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    tr_denoise::denoise(static_cast<hipStream_t>(stream_), even_dev, odd_dev, width, height, radius, patch, k, out_dev, scratch_dev);
+    HIP_CHECK(hipGetLastError());
     return TRAY_OK;
 }
 

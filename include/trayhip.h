@@ -412,6 +412,45 @@ uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height);
 int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                         float* out_dev, void* scratch_dev, void* stream);
 
+/* The two cross-filtered halves of tray_denoise_device's statement as RGBW films: fa = (A(p), wA), fb = (B(p), wB), where wA = 1 if A's denominator
+ * sum_q w_b(p, q) is > 0, else 0 (then A = 0), wB likewise. (fa.rgb + fb.rgb) * 0.5f is tray_denoise_device's out.rgb, bit for bit.
+ * |fa - fb| / 2 is a per-pixel confidence map of the denoised frame: the two halves are two estimates of the same image.
+ * blocks_dev: null = every pixel; else n_blocks indices (row-major, tiles_x = ceil(width / 32)) of 32 x 16 pixel blocks: only those are computed and
+ * written, every other pixel of fa / fb is left as it is. An index outside the frame's blocks is passed over. n_blocks == 0 with a list is valid
+ * and launches nothing; with a null list n_blocks is not read.
+ * The argument rules are tray_denoise_device's and the scratch size is tray_denoise_scratch_bytes; the two films, the two outputs and the scratch
+ * must be five different buffers, 16-byte aligned; a list longer than the frame has blocks is TRAY_E_INVALID. Three launches on `stream`
+ * (tray_denoise_device's two preparing ones and the filter), asynchronous, on the current device. No atomics: the same bits in every run. */
+#define TRAY_DENOISE_BLOCK_W 32
+#define TRAY_DENOISE_BLOCK_H 16
+int tray_denoise_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                               const uint32_t* blocks_dev, uint32_t n_blocks, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream);
+
+/* tray_render_noise_target_device with the stopping rule on the image that will be shown: the rounds, the even / odd split, n_t, the outputs,
+ * TrayKernelTiming and the error returns are that call's, word for word, and the films it returns are still the unfiltered films of exactly
+ * [0, n_t) of every tile. One thing differs: the error of a tile in a round is that call's metric evaluated on (fa, fb) =
+ * tray_denoise_halves_device(radius, patch, k) of the films as they stand after that round, in place of (even, odd): e = fa.rgb, o = fb.rgb, and
+ * a pixel with wA = 0 or wB = 0 counts as +inf, as a pixel without weight does there. The difference of the filtered halves estimates the
+ * residual error of the denoised image (Rousselle, Knaus, Zwicker 2012), so samples go where the filter cannot repair the noise. A border pixel
+ * whose film weight ended <= 0 is filled by the filter and no longer keeps its tile sampling up to max_spp.
+ * - Each round filters only the 32 x 16 blocks that hold an active tile (round 0: a tile of the selected range); the host reads the number of
+ *   active tiles and of blocks in its one copy and synchronisation per round, plus one before round 0 for that round's block count.
+ * - out_dev (may be null): with it the call ends with tray_denoise_device's three launches on the final films, inside the call's timing, so
+ *   out_dev equals a separate tray_denoise_device call's output bit for bit.
+ * - scratch_dev: tray_noise_target_filtered_scratch_bytes(width, height) bytes of the scene's film size (the filter's 48 bytes per pixel, fa
+ *   and fb, the block flags, list and counts; 0 if width or height is 0). Its layout is private.
+ * - Determinism is tray_render_noise_target_device's: the films are sums of float atomics, so a tile whose error lies within rounding of
+ *   `threshold` may be decided either way from one run to the next; what is returned is always the film of exactly the reported [0, n_t).
+ * - A stopped tile's reported error is that of the round it stopped in. Its filter window then still held its neighbours' earlier samples: the
+ *   error is the metric of the halves of the returned films only for the tiles that were computed in the call's last round.
+ * Returns TRAY_E_INVALID under tray_render_noise_target_device's rules and tray_denoise_device's for radius, patch and k, if scratch_dev is null,
+ * or unless the films, the scratch and (if given) the output are different buffers, 16-byte aligned; TRAY_E_UNSUPPORTED as that call. */
+uint64_t tray_noise_target_filtered_scratch_bytes(uint32_t width, uint32_t height);
+int tray_render_noise_target_filtered_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp,
+                                             float threshold, uint64_t seed, float* even_dev, float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                                             float* out_dev /* may be null */, void* scratch_dev, uint32_t* tile_samples, float* tile_error,
+                                             void* stream);
+
 /* Host-side enumeration of the Morton-queue indices tray_render_shard_device renders for `shard`
  * (same mapping; lets callers and tests reason about the partition without a GPU). */
 int tray_shard_tiles(uint32_t n_tiles, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles,

@@ -285,31 +285,56 @@ class Hip:
                     self.last_timing = t
                 yield end, rt
 
-    def render_noise_target(self, scene, rt, config, threshold, min_spp=16):
+    def _noise_target_device(self, dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out):
+        """one noise-target call on the current stream into the zeroed (h, w, 4) tensors even / odd: error="raw" is
+        tray_render_noise_target_device, "filtered" tray_render_noise_target_filtered_device (with its denoised output if want_out). Returns
+        (tile_samples, tile_error, out tensor or None)."""
+        import torch
+        samples, err = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        sp, ep = samples.ctypes.data_as(C.POINTER(C.c_uint32)), err.ctypes.data_as(C.POINTER(C.c_float))
+        stream = torch.cuda.current_stream().cuda_stream
+        stream = C.c_void_p(stream) if stream else None
+        out = None
+        if error == "raw":
+            check(lib().tray_render_noise_target_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
+                                                        C.c_void_p(odd.data_ptr()), sp, ep, stream))
+        else:
+            h, w = int(even.shape[0]), int(even.shape[1])
+            scratch = torch.empty(max(int(lib().tray_noise_target_filtered_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=even.device)
+            out = torch.empty_like(even) if want_out else None
+            check(lib().tray_render_noise_target_filtered_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
+                                                                 C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k),
+                                                                 C.c_void_p(out.data_ptr()) if want_out else None, C.c_void_p(scratch.data_ptr()), sp, ep,
+                                                                 stream))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return samples, err, out
+
+    def render_noise_target(self, scene, rt, config, threshold, min_spp=16, error="raw", radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
+                            k=_lib.TRAY_DENOISE_K):
         """config.select_blocks of the frame rendered to a noise threshold (tray_render_noise_target_device): every tile takes the
         power-of-two prefix [0, n_t) of the round_spp(config.spp)-sample LowDiscrepancy frame, min_spp <= n_t <= that spp, at which its
-        two-buffer error drops below `threshold`. The image (even + odd film) is added into rt. Returns (tile_samples, tile_error): numpy
-        arrays of n_t and the last error per tile, in BlockQueue order. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        two-buffer error drops below `threshold`. error="filtered" takes that error from the two cross-filtered halves of the films instead
+        (tray_render_noise_target_filtered_device with radius, patch, k): the rule for a frame that will be denoised. The image (even + odd film,
+        unfiltered either way) is added into rt. Returns (tile_samples, tile_error): numpy arrays of n_t and the last error per tile, in BlockQueue
+        order. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
         import torch
+        if error not in ("raw", "filtered"):
+            raise ValueError(f"error must be 'raw' or 'filtered', not {error!r}")
         dev = scene.device_scene(config.current_frame, self.device)
         spp = self._select_sampler(dev, config.spp)
         start, count = (int(v) for v in config.select_blocks)
         w, h = rt.dimensions()
         n = len(BlockQueue((w, h), (8, 8), (start, count)).blocks)
-        samples, error = np.zeros(n, np.uint32), np.zeros(n, np.float32)
         with torch.cuda.device(self.device):
-            even = torch.zeros(h * w * 4, dtype=torch.float32, device=f"cuda:{self.device}")
+            even = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
             odd = torch.zeros_like(even)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_render_noise_target_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
-                                                        C.c_void_p(odd.data_ptr()), samples.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                        error.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(stream) if stream else None))
-            rt.add_pixels((even + odd).cpu().numpy())
+            samples, err, _ = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, False)
+            rt.add_pixels((even + odd).reshape(-1).cpu().numpy())
         t = _lib.TrayKernelTiming()
         if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
             self.last_timing = t
             print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
-        return samples, error
+        return samples, err
 
     def _denoise_device(self, even, odd, radius, patch, k):
         """tray_denoise_device of two (h, w, 4) float32 tensors of this device on the current stream; returns the output tensor"""
@@ -325,40 +350,68 @@ class Hip:
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out
 
-    def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
-        """The dual-buffer NL-means filter of include/trayhip.h (tray_denoise_device) of two half films, e.g. the even and odd film of a
-        noise-target render: two (h, w, 4) float32 RGBW arrays -- numpy arrays or torch tensors on this device -- in, the same kind out: an RGBW
-        film of weight 1. Pixels of weight <= 0 or with a non-finite component count as missing and are filled from their neighbourhood."""
+    def _films_on_device(self, what, even, odd):
+        """(as_numpy, e, o): two (h, w, 4) films -- numpy arrays or torch tensors on this device -- as two contiguous float32 tensors"""
         import torch
         as_numpy = isinstance(even, np.ndarray)
         if as_numpy != isinstance(odd, np.ndarray):
-            raise TypeError("denoise: even and odd must both be numpy arrays or both be torch tensors")
+            raise TypeError(f"{what}: even and odd must both be numpy arrays or both be torch tensors")
         dev = f"cuda:{self.device}"
         if as_numpy:
             e, o = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) for x in (even, odd))
         else:
             if even.device != torch.device(dev) or odd.device != torch.device(dev):
-                raise ValueError(f"denoise: the films must live on {dev}")
+                raise ValueError(f"{what}: the films must live on {dev}")
             e, o = (x.to(torch.float32).contiguous() for x in (even, odd))
             if o.data_ptr() == e.data_ptr():
                 o = o.clone()
         if e.dim() != 3 or e.shape[2] != 4 or e.shape != o.shape:
-            raise ValueError("denoise: even and odd must be two (h, w, 4) films of one size")
+            raise ValueError(f"{what}: even and odd must be two (h, w, 4) films of one size")
+        return as_numpy, e, o
+
+    def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+        """The dual-buffer NL-means filter of include/trayhip.h (tray_denoise_device) of two half films, e.g. the even and odd film of a
+        noise-target render: two (h, w, 4) float32 RGBW arrays -- numpy arrays or torch tensors on this device -- in, the same kind out: an RGBW
+        film of weight 1. Pixels of weight <= 0 or with a non-finite component count as missing and are filled from their neighbourhood."""
+        as_numpy, e, o = self._films_on_device("denoise", even, odd)
         out = self._denoise_device(e, o, radius, patch, k)
         return out.cpu().numpy() if as_numpy else out
 
-    def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
-                        k=_lib.TRAY_DENOISE_K):
-        """config.select_blocks of the frame rendered as two half films and denoised on the device (tray_denoise_device); the RGBW output (weight 1)
-        is added into rt. With `threshold` the films are the even / odd film of tray_render_noise_target_device (see render_noise_target) and
-        (tile_samples, tile_error) is returned; without it they are the sample ranges [0, spp / 2) and [spp / 2, spp) of the
-        round_spp(config.spp)-sample frame (spp >= 2) and None is returned. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+    def denoise_halves(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+        """The two cross-filtered halves (A, B) of denoise()'s filter (tray_denoise_halves_device), films in and out as there: (A.rgb + B.rgb) / 2
+        is denoise()'s image to the bit, a half's weight is 1 where it exists and 0 where no neighbour had weight, and |A - B| / 2 is a per-pixel
+        confidence map of the denoised frame."""
         import torch
+        as_numpy, e, o = self._films_on_device("denoise_halves", even, odd)
+        h, w = int(e.shape[0]), int(e.shape[1])
+        with torch.cuda.device(self.device):
+            fa, fb = torch.empty_like(e), torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_halves_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), int(radius), int(patch), float(k), None, 0,
+                                                   C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                                   C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
+
+    def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
+                        k=_lib.TRAY_DENOISE_K, error="raw"):
+        """config.select_blocks of the frame rendered as two half films and denoised on the device (tray_denoise_device); the RGBW output (weight 1)
+        is added into rt. With `threshold` the films are the even / odd film of a noise-target render (see render_noise_target; error="filtered"
+        stops on the error of the denoised image and takes the output from that same call) and (tile_samples, tile_error) is returned; without it
+        they are the sample ranges [0, spp / 2) and [spp / 2, spp) of the round_spp(config.spp)-sample frame (spp >= 2) and None is returned.
+        LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        import torch
+        if error not in ("raw", "filtered"):
+            raise ValueError(f"error must be 'raw' or 'filtered', not {error!r}")
+        if error == "filtered" and threshold is None:
+            raise ValueError("render_denoised: error='filtered' is a stopping rule and needs a threshold")
         dev = scene.device_scene(config.current_frame, self.device)
         spp = self._select_sampler(dev, config.spp)
         start, count = (int(v) for v in config.select_blocks)
         w, h = rt.dimensions()
-        result = None
+        result, out = None, None
         with torch.cuda.device(self.device):
             even = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
             odd = torch.zeros_like(even)
@@ -370,15 +423,14 @@ class Hip:
                     self.render_samples_device(scene, config.current_frame, (start, count), spp, rng, film.data_ptr(), stream or None)
             else:
                 n = len(BlockQueue((w, h), (8, 8), (start, count)).blocks)
-                samples, error = np.zeros(n, np.uint32), np.zeros(n, np.float32)
-                check(lib().tray_render_noise_target_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
-                                                            C.c_void_p(odd.data_ptr()), samples.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                            error.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(stream) if stream else None))
-                result = (samples, error)
+                samples, err, out = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, True)
+                result = (samples, err)
             t = _lib.TrayKernelTiming()
             if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:   # (the last render call's: the whole noise-target call, or the second range)
                 self.last_timing = t
-            rt.add_pixels(self._denoise_device(even, odd, radius, patch, k).cpu().numpy())
+            if out is None:
+                out = self._denoise_device(even, odd, radius, patch, k)
+            rt.add_pixels(out.reshape(-1).cpu().numpy())
         return result
 
     def render_shard_device(self, scene, frame, shard, n_shards, spp, rgbw_ptr, chunk_tiles=16, stream=None):

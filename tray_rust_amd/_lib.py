@@ -184,6 +184,12 @@ SYMBOLS = {
                                                   C.c_void_p, _P(C.c_uint32), _P(C.c_float), C.c_void_p]),
     "tray_denoise_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "tray_denoise_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_denoise_halves_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_noise_target_filtered_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_render_noise_target_filtered_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint64, C.c_void_p,
+                                                           C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, _P(C.c_uint32),
+                                                           _P(C.c_float), C.c_void_p]),
     "tray_multi_set_partition": (C.c_int, [C.c_void_p, C.c_int]),
     "tray_multi_shard_samples": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "tray_shard_tiles": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), C.c_uint32, _P(C.c_uint32)]),

@@ -10,6 +10,7 @@
 #include "kernel_ranges.h"
 #include "noise.h"
 #include "denoise.h"
+#include "guide.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 
@@ -81,7 +82,8 @@ struct LaunchBuffers {
 };
 // tray_render_noise_target_device's per-tile state, n_tiles entries each, in one allocation made on first use: the round's tile list (coordinates and
 // queue indices; the error kernel reads it before the compaction rewrites it, in stream order, so one list serves every round), the next-round flags,
-// the samples taken and the errors (by queue index), and the list's length; h_count is the pinned word the host reads it into once per round
+// the samples taken and the errors (by queue index), and the list's length; h_count is the pinned pair of words the host reads the round's counts into (the
+// tile list's length; behind it, for the filtered rule, the block list's)
 struct NoiseBuffers {
     void* mem = nullptr;
     uint2* list = nullptr;
@@ -1092,15 +1094,64 @@ int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t
     return launch_tiles(s, s->d_tiles + tile_start, w.work, w.chunk, w.chunk_stride, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
 }
 
-// tray_render_noise_target_device's rounds over queue[0, tile_count) (include/trayhip.h), with s->accumulate set: round r renders [a, b) --
-// [0, min_spp), then [min_spp 2^(r-1), min_spp 2^r) -- of the active tiles, [a, m) into even and [m, b) into odd, then k_noise_error writes every
-// active tile's error, samples and flag, k_noise_compact the next list in queue order, and the host reads its length once.
+// What the filtered stopping rule adds to a round (tray_render_noise_target_filtered_device): the filter's arguments and the private scratch layout
+// [filter records: 48 bytes per pixel | fa | fb: RGBW films | flags | list: one word per 32 x 16 block | counts: tiles, blocks, 2 words of padding]
+struct GuideRounds {
+    uint32_t radius, patch;
+    float k;
+    void* records;
+    float* fa, * fb;
+    uint32_t* flags, * list, * counts;
+};
+static uint64_t guide_scratch_bytes(uint32_t width, uint32_t height) {
+    if (width == 0u || height == 0u) return 0u;
+    return tr_denoise::scratch_bytes(width, height) + (uint64_t)width * height * 32u + (uint64_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height) * 8u + 16u;
+}
+static GuideRounds guide_layout(void* scratch, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k) {
+    const size_t px = (size_t)width * height, nb = (size_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height);
+    GuideRounds g{};
+    g.radius = radius; g.patch = patch; g.k = k;
+    g.records = scratch;
+    g.fa = reinterpret_cast<float*>(static_cast<char*>(scratch) + tr_denoise::scratch_bytes(width, height));
+    g.fb = g.fa + 4u * px;
+    g.flags = reinterpret_cast<uint32_t*>(g.fb + 4u * px);
+    g.list = g.flags + nb;
+    g.counts = g.list + nb;
+    return g;
+}
+
+// The next round's block list of the filtered rule: the blocks that hold a tile of queue[0, tile_count) whose flag is set (active == null: every
+// tile), in row-major order, their number into g.counts[1]. Two launches.
+static int guide_block_list(const GuideRounds& g, hipStream_t stream, const uint2* queue, const uint32_t* active, uint32_t tile_count, uint32_t width,
+                            uint32_t height) {
+    HIP_CHECK(hipMemsetAsync(g.flags, 0, (size_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height) * sizeof(uint32_t), stream));
+    tr_guide::mark(stream, queue, active, tile_count, width, height, g.flags);
+    tr_guide::compact(stream, g.flags, width, height, g.list, g.counts + 1);
+    return TRAY_OK;
+}
+
+// The rounds of tray_render_noise_target_device and tray_render_noise_target_filtered_device over queue[0, tile_count) (include/trayhip.h), with
+// s->accumulate set: round r renders [a, b) -- [0, min_spp), then [min_spp 2^(r-1), min_spp 2^r) -- of the active tiles, [a, m) into even and [m, b)
+// into odd, then k_noise_error writes every active tile's error, samples and flag, k_noise_compact the next list in queue order, and the host reads
+// its length once. With g (the filtered rule) the error kernel reads the filtered halves of the films as they stand, computed over the blocks that
+// hold an active tile, and the round also makes the next block list; the host reads both lengths in its one copy.
 static int noise_rounds(TrayDeviceScene* s, const uint2* queue, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold, uint64_t seed,
-                        float* even_dev, float* odd_dev, hipStream_t stream, uint32_t* launches) {
+                        float* even_dev, float* odd_dev, const GuideRounds* g, hipStream_t stream, uint32_t* launches) {
     NoiseBuffers& b = s->nt;
+    const uint32_t width = s->dev.width, height = s->dev.height;
     const uint2* list = queue;        // round 0: the whole range, queue index = list index
     const uint32_t* list_q = nullptr;
-    uint32_t n_active = tile_count;
+    uint32_t n_active = tile_count, n_blocks = 0u;
+    uint32_t* const d_counts = g ? g->counts : b.d_count;
+    if (g) {   // round 0's blocks: those that hold a tile of the range
+        const int rc = guide_block_list(*g, stream, queue, nullptr, tile_count, width, height);
+        if (rc != TRAY_OK) return rc;
+        *launches += 2u;
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(b.h_count + 1, d_counts + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        n_blocks = b.h_count[1];
+    }
     for (uint32_t lo = 0u, hi = min_spp;; lo = hi, hi *= 2u) {
         const uint32_t mid = lo + (hi - lo) / 2u;
         int rc = launch_tiles(s, list, n_active, n_active, 1u, max_spp, seed, even_dev, stream, lo, mid);
@@ -1109,30 +1160,38 @@ static int noise_rounds(TrayDeviceScene* s, const uint2* queue, uint32_t tile_co
         rc = launch_tiles(s, list, n_active, n_active, 1u, max_spp, seed, odd_dev, stream, mid, hi);
         if (rc != TRAY_OK) return rc;
         *launches += s->launches;
-        tr_noise::error(stream, even_dev, odd_dev, s->dev.width, s->dev.height, list, list_q, n_active, hi, max_spp, threshold, b.err, b.active, b.samples);
-        tr_noise::compact(stream, queue, b.active, tile_count, b.list, b.list_q, b.d_count);
+        const float* fe = even_dev, * fo = odd_dev;   // the two films the error is taken from
+        if (g) {
+            if (n_blocks > tr_guide::blocks_x(width) * tr_guide::blocks_y(height)) {
+                set_error("tray_render_noise_target_filtered_device: the block list is longer than the frame has blocks"); return TRAY_E_DEVICE;
+            }
+            tr_denoise::prepare(stream, even_dev, odd_dev, width, height, g->records);
+            *launches += tr_denoise::kPrepareLaunches + tr_guide::halves(stream, g->records, width, height, g->radius, g->patch, g->k, g->list, n_blocks, g->fa, g->fb);
+            fe = g->fa; fo = g->fb;
+        }
+        tr_noise::error(stream, fe, fo, width, height, list, list_q, n_active, hi, max_spp, threshold, b.err, b.active, b.samples);
+        tr_noise::compact(stream, queue, b.active, tile_count, b.list, b.list_q, d_counts);
         *launches += 2u;
+        if (g) {
+            rc = guide_block_list(*g, stream, queue, b.active, tile_count, width, height);
+            if (rc != TRAY_OK) return rc;
+            *launches += 2u;
+        }
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(b.h_count, b.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(b.h_count, d_counts, (g ? 2u : 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        n_active = *b.h_count;
+        n_active = b.h_count[0];
+        n_blocks = b.h_count[1];
         if (n_active > tile_count) { set_error("tray_render_noise_target_device: the compacted tile list is longer than the queue"); return TRAY_E_DEVICE; }
         if (n_active == 0u || hi >= max_spp) return TRAY_OK;   // (at max_spp no flag is set: n_active is 0 there too)
         list = b.list; list_q = b.list_q;
     }
 }
 
-int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
-                                    uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
-    if (!s || !even_dev || !odd_dev || !tile_samples || !tile_error) { set_error("tray_render_noise_target_device: null argument"); return TRAY_E_INVALID; }
-    auto pow2 = [](uint32_t v) { return v != 0u && (v & (v - 1u)) == 0u; };
-    if (!pow2(min_spp) || !pow2(max_spp) || min_spp < 2u || max_spp < min_spp) {
-        set_error("tray_render_noise_target_device: min_spp and max_spp must be powers of two with 2 <= min_spp <= max_spp"); return TRAY_E_INVALID;
-    }
-    if (!(threshold >= 0.0f)) { set_error("tray_render_noise_target_device: threshold must be >= 0 (and not NaN)"); return TRAY_E_INVALID; }
-    if (even_dev == odd_dev) { set_error("tray_render_noise_target_device: the even and odd films must be different buffers"); return TRAY_E_INVALID; }
-    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error("tray_render_noise_target_device: sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
-    if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
+// The body of the two noise-target calls once their arguments are checked: the per-tile buffers on first use, the call's events and statistics, the
+// rounds, with g and out_dev the final filter of the films (tray_denoise_device's three launches), and the per-tile results.
+static int noise_target_call(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold, uint64_t seed,
+                             float* even_dev, float* odd_dev, const GuideRounds* g, float* out_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
     tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_CHECK(hipSetDevice(s->device));
@@ -1150,15 +1209,21 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
         b.err = reinterpret_cast<float*>(b.samples + n);
         b.d_count = reinterpret_cast<uint32_t*>(b.err + n);
     }
-    if (!b.h_count) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.h_count), sizeof(uint32_t), hipHostMallocDefault));
+    if (!b.h_count) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.h_count), 2u * sizeof(uint32_t), hipHostMallocDefault));
+    b.h_count[0] = b.h_count[1] = 0u;
     HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));   // (the launches below add to them: s->accumulate)
     HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
     HIP_CHECK(hipEventRecord(s->ev0, stream));
     uint32_t launches = 0u;
     s->accumulate = true;
-    const int rc = noise_rounds(s, s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, stream, &launches);
+    const int rc = noise_rounds(s, s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, g, stream, &launches);
     s->accumulate = false;
     if (rc != TRAY_OK) { s->timing_valid = false; return rc; }
+    if (g && out_dev) {
+        tr_denoise::denoise(stream, even_dev, odd_dev, s->dev.width, s->dev.height, g->radius, g->patch, g->k, out_dev, g->records);
+        launches += tr_denoise::kLaunches;
+        HIP_CHECK(hipGetLastError());
+    }
     HIP_CHECK(hipEventRecord(s->ev1, stream));
     HIP_CHECK(hipMemcpyAsync(tile_samples, b.samples, (size_t)tile_count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(tile_error, b.err, (size_t)tile_count * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -1168,14 +1233,95 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
     return TRAY_OK;
 }
 
+// the argument rules the two noise-target calls share; `who` names the call in the message
+static int noise_target_args(const char* who, TrayDeviceScene* s, uint32_t min_spp, uint32_t max_spp, float threshold, const float* even_dev,
+                             const float* odd_dev, const uint32_t* tile_samples, const float* tile_error) {
+    const std::string w(who);
+    if (!s || !even_dev || !odd_dev || !tile_samples || !tile_error) { set_error(w + ": null argument"); return TRAY_E_INVALID; }
+    auto pow2 = [](uint32_t v) { return v != 0u && (v & (v - 1u)) == 0u; };
+    if (!pow2(min_spp) || !pow2(max_spp) || min_spp < 2u || max_spp < min_spp) {
+        set_error(w + ": min_spp and max_spp must be powers of two with 2 <= min_spp <= max_spp"); return TRAY_E_INVALID;
+    }
+    if (!(threshold >= 0.0f)) { set_error(w + ": threshold must be >= 0 (and not NaN)"); return TRAY_E_INVALID; }
+    if (even_dev == odd_dev) { set_error(w + ": the even and odd films must be different buffers"); return TRAY_E_INVALID; }
+    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error(w + ": sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
+    if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
+    return TRAY_OK;
+}
+
+int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
+                                    uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
+    const int rc = noise_target_args("tray_render_noise_target_device", s, min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
+    if (rc != TRAY_OK) return rc;
+    return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, nullptr, nullptr, tile_samples, tile_error, stream_);
+}
+
+// the filter's own argument rules (tray_denoise_device's), shared by the calls that take them
+static int denoise_args(const char* who, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k) {
+    const std::string w(who);
+    if (width == 0u || height == 0u) { set_error(w + ": width and height must be >= 1"); return TRAY_E_INVALID; }
+    if (radius < 1u || radius > 10u || patch > 3u) { set_error(w + ": 1 <= radius <= 10 and patch <= 3 are required"); return TRAY_E_INVALID; }
+    if (!(k > 0.0f) || !std::isfinite(k)) { set_error(w + ": k must be > 0 and finite"); return TRAY_E_INVALID; }
+    return TRAY_OK;
+}
+// n buffers, pairwise different and 16-byte aligned
+static bool distinct_aligned(const void* const* bufs, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        if (reinterpret_cast<uintptr_t>(bufs[i]) & 15u) return false;
+        for (size_t j = 0; j < i; ++j)
+            if (bufs[i] == bufs[j]) return false;
+    }
+    return true;
+}
+
+uint64_t tray_noise_target_filtered_scratch_bytes(uint32_t width, uint32_t height) { return guide_scratch_bytes(width, height); }
+
+int tray_render_noise_target_filtered_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
+                                             uint64_t seed, float* even_dev, float* odd_dev, uint32_t radius, uint32_t patch, float k, float* out_dev,
+                                             void* scratch_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
+    const char* const who = "tray_render_noise_target_filtered_device";
+    int rc = noise_target_args(who, s, min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
+    if (rc != TRAY_OK) return rc;
+    if (!scratch_dev) { set_error(std::string(who) + ": null argument"); return TRAY_E_INVALID; }
+    rc = denoise_args(who, s->dev.width, s->dev.height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    const void* const bufs[4] = {even_dev, odd_dev, scratch_dev, out_dev};
+    if (!distinct_aligned(bufs, out_dev ? 4u : 3u)) {
+        set_error(std::string(who) + ": the films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    const GuideRounds g = guide_layout(scratch_dev, s->dev.width, s->dev.height, radius, patch, k);
+    return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, &g, out_dev, tile_samples, tile_error, stream_);
+}
+
+int tray_denoise_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                               const uint32_t* blocks_dev, uint32_t n_blocks, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
+    const char* const who = "tray_denoise_halves_device";
+    if (!even_dev || !odd_dev || !fa_dev || !fb_dev || !scratch_dev) { set_error(std::string(who) + ": null argument"); return TRAY_E_INVALID; }
+    const int rc = denoise_args(who, width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    const void* const bufs[5] = {even_dev, odd_dev, fa_dev, fb_dev, scratch_dev};
+    if (!distinct_aligned(bufs, 5u)) {
+        set_error(std::string(who) + ": the two films, the two outputs and the scratch buffer must be five different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    if (blocks_dev && n_blocks > tr_guide::blocks_x(width) * tr_guide::blocks_y(height)) {
+        set_error(std::string(who) + ": the block list is longer than the frame has blocks"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (blocks_dev && n_blocks == 0u) return TRAY_OK;   // (nothing to compute: no launch at all)
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, scratch_dev);
+    tr_guide::halves(stream, scratch_dev, width, height, radius, patch, k, blocks_dev, n_blocks, fa_dev, fb_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
 uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height) { return tr_denoise::scratch_bytes(width, height); }
 
 int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                         float* out_dev, void* scratch_dev, void* stream_) {
     if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error("tray_denoise_device: null argument"); return TRAY_E_INVALID; }
-    if (width == 0u || height == 0u) { set_error("tray_denoise_device: width and height must be >= 1"); return TRAY_E_INVALID; }
-    if (radius < 1u || radius > 10u || patch > 3u) { set_error("tray_denoise_device: 1 <= radius <= 10 and patch <= 3 are required"); return TRAY_E_INVALID; }
-    if (!(k > 0.0f) || !std::isfinite(k)) { set_error("tray_denoise_device: k must be > 0 and finite"); return TRAY_E_INVALID; }
+    const int rc = denoise_args("tray_denoise_device", width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
     if (even_dev == odd_dev || out_dev == even_dev || out_dev == odd_dev) {
         set_error("tray_denoise_device: the two films and the output must be three different buffers"); return TRAY_E_INVALID;
     }

@@ -1,7 +1,12 @@
 """The dual-buffer NL-means filter of tray_denoise_device (include/trayhip.h) as a numpy statement, typed: denoise(E, O, r, f, k, F) evaluates
 it in F = np.float32 (the arithmetic the kernels do, in numpy's order of summation) or F = np.float64 (what the tests compare with). Also the
-test films, the bar of the comparisons and the range property, shared by the CPU and the GPU tests of the denoiser."""
+test films, the bar of the comparisons and the range property, shared by the CPU and the GPU tests of the denoiser, and the GPU tests' one call
+of tray_denoise_device between guard bytes and their many-sample reference image (torch is imported there, where a GPU is used)."""
+import ctypes as C
+
 import numpy as np
+
+import tray_rust_amd as T
 
 F32, F64 = np.float32, np.float64
 EPS = 1e-7
@@ -164,3 +169,47 @@ def range_violations(out_rgb, E, O, r, where=None):
     o = np.asarray(out_rgb, F64)
     bad = (o < wlo - slack * mag) | (o > whi + slack * mag)
     return np.argwhere(bad.any(-1) & (valid if where is None else np.asarray(where, bool)))
+
+
+def rgb(img):
+    with np.errstate(all="ignore"):
+        return np.where(img[..., 3:] > 0, img[..., :3] / img[..., 3:], 0).astype(F32)
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
+
+
+# ---- on the GPU
+
+GPU_GUARD = 4096   # bytes
+
+
+def denoise_guarded(even, odd, r, f, k):
+    """one tray_denoise_device call on films uploaded from the host, its output and scratch buffer between guard bytes; returns (h, w, 4)"""
+    import torch
+    GUARD = GPU_GUARD
+    h, w = even.shape[:2]
+    lib = T.lib()
+    e, o = torch.from_numpy(np.ascontiguousarray(even)).cuda(), torch.from_numpy(np.ascontiguousarray(odd)).cuda()
+    nb = int(lib.tray_denoise_scratch_bytes(w, h))
+    assert nb > 0
+    scr = torch.full((nb + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    out = torch.full((w * h * 16 + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    T.check(lib.tray_init(0))
+    T.check(lib.tray_denoise_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), r, f, k, C.c_void_p(out.data_ptr() + GUARD),
+                                    C.c_void_p(scr.data_ptr() + GUARD), None))
+    torch.cuda.synchronize()
+    assert (scr[:GUARD] == 0xA5).all() and (scr[GUARD + nb:] == 0xA5).all(), "a write outside tray_denoise_scratch_bytes of scratch"
+    assert (out[:GUARD] == 0xA5).all() and (out[GUARD + w * h * 16:] == 0xA5).all(), "a write outside out_dev"
+    assert (e.cpu().numpy().view(np.uint32) == even.view(np.uint32)).all() and (o.cpu().numpy().view(np.uint32) == odd.view(np.uint32)).all()
+    return out[GUARD:GUARD + w * h * 16].view(torch.float32).reshape(h, w, 4).cpu().numpy()
+
+
+def reference_image(scene, spp, seed):
+    import torch
+    fl = scene.flatten(0).contents.film
+    film = torch.zeros(fl.width * fl.height * 4, dtype=torch.float32, device="cuda:0")
+    T.Hip(0, seed=seed).render_device(scene, 0, (0, 0), spp, film.data_ptr())
+    torch.cuda.synchronize()
+    return rgb(film.cpu().numpy().reshape(fl.height, fl.width, 4))

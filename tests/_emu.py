@@ -19,41 +19,50 @@ def _stale(so, deps):
     return not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps)
 
 
-def _target(defines):
-    so = os.path.join(EMU_DIR, "libtrayemu" + "".join("_" + d.lower() for d in defines).replace("_tr_", "_") + ".so")
-    deps = [os.path.join(EMU_DIR, f) for f in ("emu_kernels.cpp", "hip_emu.h")]
-    deps += [os.path.join(HIP_DIR, f) for f in os.listdir(HIP_DIR) if f.endswith((".h", ".hip"))]
-    deps += [os.path.join(ROOT, "tray_rust_amd", "csrc", "host", "gates.hpp"), os.path.join(ROOT, "include", "trayhip.h")]
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-attributes", "-shared", "-o", so,
-           os.path.join(EMU_DIR, "emu_kernels.cpp")] + ["-D" + d for d in defines]
-    return so, deps, cmd
+def device_deps():
+    """what emu_kernels.cpp is compiled from besides itself: the shim, every device source and header, and the two headers they share with the host"""
+    deps = [os.path.join(EMU_DIR, "hip_emu.h")] + [os.path.join(HIP_DIR, f) for f in os.listdir(HIP_DIR) if f.endswith((".h", ".hip"))]
+    return deps + [os.path.join(ROOT, "tray_rust_amd", "csrc", "host", "gates.hpp"), os.path.join(ROOT, "include", "trayhip.h")]
 
 
-def _norm(defines):
-    return tuple(sorted(set(defines)))
+def _start_build(so, src, deps, defines=()):
+    """(path of tests/emu/<so>, the running g++ or None): compiles it from tests/emu/<src> if it is missing or older than the source or one of deps"""
+    so, src = os.path.join(EMU_DIR, so), os.path.join(EMU_DIR, src)
+    if not _stale(so, [src] + list(deps)):
+        return so, None
+    return so, subprocess.Popen(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-attributes", "-shared", "-o", so, src]
+                                + ["-D" + d for d in defines])
+
+
+def _finish(proc):
+    if proc is not None and proc.wait() != 0:
+        raise RuntimeError("host emulation build failed: " + " ".join(proc.args))
+
+
+def build(so, src, deps, defines=()):
+    """the one build of an emulation library (the feature libraries' loaders are in tests/_emu_features.py); returns its path"""
+    so, proc = _start_build(so, src, deps, defines)
+    _finish(proc)
+    return so
+
+
+def _kernels(defines):
+    """build()'s arguments for emu_kernels.cpp with the given macros"""
+    defines = tuple(sorted(set(defines)))
+    return "libtrayemu" + "".join("_" + d.lower() for d in defines).replace("_tr_", "_") + ".so", "emu_kernels.cpp", device_deps(), defines
 
 
 def prebuild(define_sets):
     """compile the stale ones of several builds side by side (each takes ~25 s; the suite uses five)"""
-    procs = []
-    for defines in define_sets:
-        so, deps, cmd = _target(_norm(defines))
-        if _stale(so, deps):
-            procs.append((cmd, subprocess.Popen(cmd)))
-    for cmd, p in procs:
-        if p.wait() != 0:
-            raise RuntimeError("host emulation build failed: " + " ".join(cmd))
+    for proc in [_start_build(*_kernels(defines))[1] for defines in define_sets]:
+        _finish(proc)
 
 
 def emu(defines=()):
     """libtrayemu.so, or a build of the same sources with extra macros (defines=("TR_...",))"""
-    defines = _norm(defines)
-    key = defines
+    key = tuple(sorted(set(defines)))
     if key not in _libs:
-        so, deps, cmd = _target(defines)
-        if _stale(so, deps):
-            subprocess.run(cmd, check=True)
-        h = C.CDLL(so)
+        h = C.CDLL(build(*_kernels(key)))
         FS = C.POINTER(L.TrayFlatScene)
         h.emu_debug_intersect.restype = C.c_int
         h.emu_debug_intersect.argtypes = [FS, C.c_uint32, C.c_void_p, C.c_void_p]

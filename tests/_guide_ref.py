@@ -98,3 +98,13 @@ def block_mask(blocks, width, height):
         x0, y0 = (b % bx) * BW, (b // bx) * BH
         mask[y0:y0 + BH, x0:x0 + BW] = True
     return mask
+
+
+def block_lists(w, h):
+    """the block lists the tests of a listed call go through, by name"""
+    bx, by = blocks_of(w, h)
+    n = bx * by
+    rng = np.random.default_rng(w + h)
+    last = sorted(set(range(bx - 1, n, bx)) | set(range((by - 1) * bx, n)))   # the last column and the last row
+    return {"empty": [], "last-row-and-column": last, "all": list(range(n)), "scattered": sorted(rng.choice(n, max(1, n // 3), replace=False).tolist()),
+            "unordered-with-one-outside": [n - 1, 0, n + 5]}

@@ -6,8 +6,13 @@
  * matters for the plumbing is appended to the log file named by FAKEHIP_LOG.
  * tests/test_launch_buffers_stub.py drives a device scene's launch buffers (wavefront pool, transform cache and table) with three more switches:
  * FAKEHIP_FREE_BYTES (what hipMemGetInfo reports free), FAKEHIP_MALLOC_MAX (hipMalloc refuses anything larger) and FAKEHIP_WF_DONE (a 4-byte
- * device-to-host copy -- the wavefront schedule's "tiles done" poll -- reads UINT32_MAX, so that a launch of kernels that do nothing ends). */
+ * device-to-host copy -- the wavefront schedule's "tiles done" poll -- reads UINT32_MAX, so that a launch of kernels that do nothing ends).
+ * A launch is logged by the library its kernel lives in (dladdr of the host stub): "guide" / "denoise" / "noise ... kernel=<symbol>" for the
+ * add-on libraries (tests/test_guide_stub.py, test_denoise_stub.py, test_noise_target_stub.py), "launch" for everything else; under
+ * FAKEHIP_TILE_KERNEL=1 a "range dev=.. begin=.. end=.." line goes in front of the tile kernel's "launch" line (tests/test_sample_ranges_stub.py).
+ * A new add-on library gets a branch of its own in hipLaunchKernel. tests/_stub.py builds and preloads this file. */
 #define _GNU_SOURCE
+#include <dlfcn.h>
 #include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -85,13 +90,40 @@ static __thread struct { dim3 g, b; size_t sh; hipStream_t st; } t_cfg;
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t st) { t_cfg.g = g; t_cfg.b = b; t_cfg.sh = sh; t_cfg.st = st; return 0; }
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* st) { *g = t_cfg.g; *b = t_cfg.b; *sh = t_cfg.sh; *st = t_cfg.st; return 0; }
 hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** args, size_t sh, hipStream_t st) {
-    (void)f; (void)sh;
+    (void)sh;
+    Dl_info di;
+    const int found = dladdr(f, &di) && di.dli_fname;
+    const char* const sym = found && di.dli_sname ? di.dli_sname : "?";
+    /* the add-on libraries' kernels are no tile kernels: their arguments are neither read nor written, with one exception -- a k_guide_compact
+     * launch (flags, n, list, count) answers as if every flag were set (list = 0 .. n - 1, *count = n), so that the round that follows filters
+     * every block of the frame and the launch shows in the log */
+    if (found && strstr(di.dli_fname, "libtrayhip_guide") != NULL) {
+        logf_("guide dev=%d grid=%u block=%u stream=%p kernel=%s", t_device, g.x, b.x, st, sym);
+        if (strstr(sym, "k_guide_compact") != NULL) {
+            const uint32_t n = *(uint32_t*)args[1];
+            uint32_t* const list = *(uint32_t**)args[2];
+            for (uint32_t i = 0; i < n; ++i) list[i] = i;
+            **(uint32_t**)args[3] = n;
+        }
+        return 0;
+    }
+    if (found && strstr(di.dli_fname, "libtrayhip_denoise") != NULL) {
+        logf_("denoise dev=%d grid=%u block=%u stream=%p kernel=%s", t_device, g.x, b.x, st, sym);
+        return 0;
+    }
+    if (found && strstr(di.dli_fname, "libtrayhip_noise") != NULL) {
+        logf_("noise dev=%d grid=%u block=%u kernel=%s", t_device, g.x, b.x, sym);
+        return 0;
+    }
     /* FAKEHIP_TILE_KERNEL=1: the launch is k_path_tiles(scene, tiles, tile_count, chunk, chunk_stride, spp, kf, slice_shift, rgbw, counter, stats)
-     * (kernels.hip): log its shard arguments and leave a mark in the film -- word 0 += device + 1 -- so that the sum-reduce has something to sum */
+     * (kernels.hip), from libtrayhip_ranges.so with (sample_begin, sample_end) behind them (0 / 0 otherwise: the whole frame): log its range and
+     * its shard arguments and leave a mark in the film -- word 0 += device + 1 -- so that the sum-reduce has something to sum */
     if (getenv("FAKEHIP_TILE_KERNEL")) {
+        const int ranged = found && strstr(di.dli_fname, "libtrayhip_ranges") != NULL;
         const uint32_t tile_count = *(uint32_t*)args[2], chunk = *(uint32_t*)args[3], chunk_stride = *(uint32_t*)args[4], spp = *(uint32_t*)args[5];
         float* film = *(float**)args[8];
         film[0] += (float)(t_device + 1);
+        logf_("range dev=%d begin=%u end=%u", t_device, ranged ? *(uint32_t*)args[11] : 0u, ranged ? *(uint32_t*)args[12] : 0u);
         logf_("launch dev=%d grid=%u block=%u stream=%p tile_count=%u chunk=%u chunk_stride=%u spp=%u film=%p", t_device, g.x, b.x, st, tile_count, chunk, chunk_stride, spp, (void*)film);
     } else logf_("launch dev=%d grid=%u block=%u stream=%p", t_device, g.x, b.x, st);
     return 0;

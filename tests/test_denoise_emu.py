@@ -7,57 +7,27 @@ the f32 numpy statement differs from it on the same input, plus 1e-7 (they sum 4
 numpy); validity decisions agree exactly. Then the properties the header states (range, a noise-free film, a constant colour, degenerate
 films), and that the filter denoises films of the oracle: RMSE(denoised) / RMSE(even + odd) against a 2048-spp oracle render is 0.598 on
 cornell_box and 0.568 on smallpt (64 x 64, 32 spp, the defaults); the condition is < 1."""
-import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import tray_rust_amd as T
 from tray_rust_amd import scenes
-import _emu as E
+import _emu_features as EF
 import _oracle as O
 import _denoise_ref as D
+import _ranges as R
+from _denoise_ref import rgb, rmse
+from _emu_features import denoise as run
 
-HDR = os.path.join(E.HIP_DIR, "denoise_kernels.h")
 F32 = np.float32
-
-
-def _denoise_lib():
-    so = os.path.join(E.EMU_DIR, "libtrayemu_denoise.so")
-    src = os.path.join(E.EMU_DIR, "emu_denoise.cpp")
-    if E._stale(so, [src, os.path.join(E.EMU_DIR, "hip_emu.h"), HDR, os.path.join(E.HIP_DIR, "dev_libm.h")]):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-attributes", "-shared", "-o", so, src], check=True)
-    h = C.CDLL(so)
-    h.emu_denoise.restype = C.c_int
-    h.emu_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
-    h.emu_denoise_scratch_bytes.restype = C.c_uint64
-    h.emu_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
-    return h
 
 
 @pytest.fixture(scope="module")
 def emu():
-    return _denoise_lib()
-
-
-GUARD = 64   # floats / bytes around the output and the scratch buffer
-
-
-def run(emu, even, odd, r, f, k):
-    """the three launches of one tray_denoise_device call in the emulation; the output and the scratch buffer lie between guard words"""
-    even, odd = np.ascontiguousarray(even, F32), np.ascontiguousarray(odd, F32)
-    h, w = even.shape[:2]
-    out = np.full(h * w * 4 + 2 * GUARD, -7.0, F32)
-    nb = int(emu.emu_denoise_scratch_bytes(w, h))
-    scratch = np.full(nb + 2 * GUARD, 0xA5, np.uint8)
-    rc = emu.emu_denoise(even.ctypes.data, odd.ctypes.data, w, h, r, f, k, out[GUARD:].ctypes.data, scratch[GUARD:].ctypes.data)
-    assert rc == 0, rc
-    assert (out[:GUARD] == -7.0).all() and (out[-GUARD:] == -7.0).all(), "a write outside the output"
-    assert (scratch[:GUARD] == 0xA5).all() and (scratch[-GUARD:] == 0xA5).all(), "a write outside the scratch buffer"
-    return out[GUARD:-GUARD].reshape(h, w, 4).copy()
+    return EF.denoise_lib()
 
 
 SIZES = [(5, 3), (20, 12), (67, 45)]   # smaller than a window; not multiples of the 32 x 16 tile
@@ -154,33 +124,6 @@ SPP, SPLIT, REF_SPP = 32, 16, 2048
 SEED, REF_SEED = 7, 1234
 
 
-def oracle_range(flat, rng, spp, seed):
-    """the oracle's film of the samples [begin, end) of every pixel of the spp-sample frame (as tests/test_sample_ranges_emu.py: oracle_range)"""
-    fs = flat.contents
-    w, h = fs.film.width, fs.film.height
-    r = E.FILM_PATCH_R
-    pad = np.zeros((h + 2 * r, w + 2 * r, 4), F32)
-    for tile in np.array(T.BlockQueue((w, h), (8, 8)).blocks, np.uint32).reshape(-1, 2):
-        px, py = np.meshgrid(np.arange(8) + 8 * int(tile[0]), np.arange(8) + 8 * int(tile[1]))
-        px, py = np.repeat(px.ravel(), rng[1] - rng[0]), np.repeat(py.ravel(), rng[1] - rng[0])
-        si = np.tile(np.arange(rng[0], rng[1]), 64)
-        out = O.sample_radiance(flat, px, py, si, spp, seed=seed)
-        s = np.concatenate([out[:, 3:5], out[:, 0:3]], 1)
-        patches = O.film_patches(fs.film, (int(tile[0]), int(tile[1])), s, r)
-        for (x, y), p in zip(np.floor(out[:, 3:5]).astype(int), patches):
-            pad[y:y + 2 * r + 1, x:x + 2 * r + 1] += p
-    return pad[r:r + h, r:r + w].copy()
-
-
-def rgb(img):
-    with np.errstate(all="ignore"):
-        return np.where(img[..., 3:] > 0, img[..., :3] / img[..., 3:], 0).astype(F32)
-
-
-def rmse(a, b):
-    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
-
-
 @pytest.mark.parametrize("name", ["cornell_box", "smallpt"])
 def test_it_denoises_oracle_films(emu, name, tmp_path, built):
     scenes.write_assets(str(tmp_path))
@@ -189,7 +132,7 @@ def test_it_denoises_oracle_films(emu, name, tmp_path, built):
         json.dump(getattr(scenes, name)(W, H, SPP), fh)
     scene, *_ = T.Scene.load_file(p)
     flat = scene.flatten(0)
-    even, odd = oracle_range(flat, (0, SPLIT), SPP, SEED), oracle_range(flat, (SPLIT, SPP), SPP, SEED)
+    even, odd = (R.oracle_range(flat, R.tile_queue(W, H), rng, SPP, SEED)[0] for rng in ((0, SPLIT), (SPLIT, SPP)))
     ref = rgb(O.render_tiles(flat, REF_SPP, seed=REF_SEED)[0])
     r, f, k = 7, 3, 0.45
     out = run(emu, even, odd, r, f, k)

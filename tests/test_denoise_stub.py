@@ -1,17 +1,12 @@
-"""tray_denoise_device through the real library against the stand-in runtime (tests/stubs/fakehip_denoise.c: fakehip_noise.c plus one log line
-per launch of libtrayhip_denoise.so), as tests/test_noise_target_stub.py: every TRAY_E_INVALID case of include/trayhip.h,
+"""tray_denoise_device through the real library against the stand-in runtime (tests/stubs/fakehip.c: one log line per launch of
+libtrayhip_denoise.so), as tests/test_noise_target_stub.py: every TRAY_E_INVALID case of include/trayhip.h,
 tray_denoise_scratch_bytes, the three launches of a call on the caller's stream (k_dn_prepare<0>, k_dn_prepare<1>, k_dn_filter<patch> over the
 32 x 16 tiles), and tray_render_tiles_device / tray_render_noise_target_device launching what they launched before."""
 import os
-import subprocess
-import sys
 
-import pytest
-
-from test_noise_target_stub import events as noise_events, kv
+from _stub import events, stub   # (stub: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUBS = os.path.join(ROOT, "tests", "stubs")
 
 DRIVER = r'''
 import ctypes as C, os, sys
@@ -61,34 +56,15 @@ print("DONE")
 '''
 
 
-@pytest.fixture(scope="module")
-def stub(tmp_path_factory, built):
-    d = tmp_path_factory.mktemp("denoise_stub")
-    hip = str(d / "libfakehip_denoise.so")
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", hip, os.path.join(STUBS, "fakehip_denoise.c"), "-lpthread", "-ldl"], check=True)
-    return hip
-
-
 def run(stub, tmp_path, mode):
-    log = str(tmp_path / "calls.log")
-    env = dict(os.environ, LD_PRELOAD=stub, FAKEHIP_LOG=log, FAKEHIP_DEVICES="1", FAKEHIP_TILE_KERNEL="1")
-    out = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "tmp": str(tmp_path), "mode": mode}], env=env, capture_output=True, text=True,
-                         timeout=300)
+    out, log = stub(DRIVER % {"root": ROOT, "tmp": str(tmp_path), "mode": mode}, tmp_path, FAKEHIP_DEVICES=1, FAKEHIP_TILE_KERNEL=1)
     assert "DONE" in out.stdout, out.stdout + out.stderr
-    return out.stdout, open(log).read().splitlines() if os.path.exists(log) else []
+    return out.stdout, log
 
 
 def denoise_events(log):
     """the launches of libtrayhip_denoise.so in order: (kernel, template argument, grid, block, stream)"""
-    out = []
-    for l in log:
-        if l.startswith("denoise"):
-            n = kv(l)
-            sym = n["kernel"]   # _ZN10tr_denoise12k_dn_prepareILi0EEEv... / _ZN10tr_denoise11k_dn_filterILi3EEEv...
-            name = "prepare" if "k_dn_prepare" in sym else "filter" if "k_dn_filter" in sym else sym
-            arg = int(sym.split("ILi", 1)[1].split("E", 1)[0]) if "ILi" in sym else -1
-            out.append((name, arg, int(n["grid"]), int(n["block"]), n["stream"]))
-    return out
+    return [e[1:] for e in events(log) if e[0] == "denoise"]
 
 
 def test_arguments_are_checked(stub, tmp_path):
@@ -140,6 +116,6 @@ def test_renders_launch_what_they_launched_before(stub, tmp_path):
     out, log = run(stub, tmp_path, "renders")
     assert "RC_PLAIN 0" in out and "RC_NT 0" in out, out
     assert denoise_events(log) == []
-    assert noise_events(log) == [
+    assert [e for e in events(log) if e[0] in ("range", "noise")] == [
         ("range", 0, 0, 48, 16, 48, 1),
         ("range", 0, 4, 48, 64, 48, 1), ("range", 4, 8, 48, 64, 48, 1), ("noise", "error", 12, 256), ("noise", "compact", 1, 1024)]

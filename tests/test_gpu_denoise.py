@@ -5,8 +5,6 @@ statement differs from the f64 one on the same films, plus 1e-7. The generator f
 kernel and by the wavefront schedule, Hip.render_denoised against Hip.denoise of separately rendered films, and a 1920 x 1080 frame checked on
 crops. Two calls give the same bits, and guard words around the output and the scratch buffer stay intact. Nothing here reads the reference."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
@@ -14,49 +12,12 @@ import pytest
 import tray_rust_amd as T
 from tray_rust_amd import scenes
 import _denoise_ref as D
+from _denoise_ref import denoise_guarded, reference_image, rgb, rmse
+from _noise_ref import load
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
 RF = [(1, 0), (3, 1), (7, 3), (10, 3)]
-GUARD = 4096   # bytes
-
-
-def rgb(img):
-    with np.errstate(all="ignore"):
-        return np.where(img[..., 3:] > 0, img[..., :3] / img[..., 3:], 0).astype(F32)
-
-
-def rmse(a, b):
-    return float(np.sqrt(np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)))
-
-
-def load(d, tmp_path, name="s.json"):
-    scenes.write_assets(str(tmp_path))
-    p = os.path.join(str(tmp_path), name)
-    with open(p, "w") as f:
-        json.dump(d, f)
-    return T.Scene.load_file(p)
-
-
-def denoise_guarded(even, odd, r, f, k):
-    """one tray_denoise_device call on films uploaded from the host, its output and scratch buffer between guard bytes; returns (h, w, 4)"""
-    import torch
-    h, w = even.shape[:2]
-    lib = T.lib()
-    e, o = torch.from_numpy(np.ascontiguousarray(even)).cuda(), torch.from_numpy(np.ascontiguousarray(odd)).cuda()
-    nb = int(lib.tray_denoise_scratch_bytes(w, h))
-    assert nb > 0
-    scr = torch.full((nb + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    out = torch.full((w * h * 16 + 2 * GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    T.check(lib.tray_init(0))
-    T.check(lib.tray_denoise_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), r, f, k, C.c_void_p(out.data_ptr() + GUARD),
-                                    C.c_void_p(scr.data_ptr() + GUARD), None))
-    torch.cuda.synchronize()
-    assert (scr[:GUARD] == 0xA5).all() and (scr[GUARD + nb:] == 0xA5).all(), "a write outside tray_denoise_scratch_bytes of scratch"
-    assert (out[:GUARD] == 0xA5).all() and (out[GUARD + w * h * 16:] == 0xA5).all(), "a write outside out_dev"
-    assert (e.cpu().numpy().view(np.uint32) == even.view(np.uint32)).all() and (o.cpu().numpy().view(np.uint32) == odd.view(np.uint32)).all()
-    return out[GUARD:GUARD + w * h * 16].view(torch.float32).reshape(h, w, 4).cpu().numpy()
 
 
 @pytest.mark.parametrize("r,f", RF, ids=[f"r{r}f{f}" for r, f in RF])
@@ -74,12 +35,12 @@ def test_generator_films_match_the_f64_statement(built, w, h, r, f):
 
 def test_emulation_and_gpu_bits(built):
     """a finding, not a requirement: with tr::ref_expf on both sides and IEEE division the host emulation is expected to give the GPU's bits"""
-    import test_denoise_emu as EM
+    import _emu_features as EF   # (builds the emulation of the denoiser when called, here only)
     even, odd = D.random_films(67, 45, seed=5)
-    emu = EM._denoise_lib()
+    emu = EF.denoise_lib()
     for r, f in RF:
         gpu = denoise_guarded(even, odd, r, f, 0.45)
-        cpu = EM.run(emu, even, odd, r, f, 0.45)
+        cpu = EF.denoise(emu, even, odd, r, f, 0.45)
         n = int((gpu.view(np.uint32) != cpu.view(np.uint32)).sum())
         print(f"r={r} f={f}: {n} of {gpu.size} words differ between the host emulation and the GPU (max abs {np.abs(gpu - cpu).max():.3e})")
         assert np.abs(gpu - cpu).max() <= 1e-5
@@ -97,15 +58,6 @@ def range_films(hip, scene, spp):
         torch.cuda.synchronize()
         films.append(film.cpu().numpy().reshape(h, w, 4))
     return films
-
-
-def reference_image(scene, spp, seed):
-    import torch
-    fl = scene.flatten(0).contents.film
-    film = torch.zeros(fl.width * fl.height * 4, dtype=torch.float32, device="cuda:0")
-    T.Hip(0, seed=seed).render_device(scene, 0, (0, 0), spp, film.data_ptr())
-    torch.cuda.synchronize()
-    return rgb(film.cpu().numpy().reshape(fl.height, fl.width, 4))
 
 
 RENDERED = [("cornell_box", ""), ("smallpt", ""), ("cornell_box", "wave")]

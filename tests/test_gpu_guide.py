@@ -17,15 +17,14 @@ import tray_rust_amd as T
 from tray_rust_amd import scenes
 import _denoise_ref as D
 import _guide_ref as G
-import test_gpu_noise_target as NT
-from test_gpu_denoise import denoise_guarded, reference_image
-from test_noise_target_emu import assert_ulps
+import _noise_ref as NT
+from _denoise_ref import GPU_GUARD as GUARD, denoise_guarded, reference_image
+from _noise_ref import assert_ulps
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 RF = [(1, 0), (3, 1), (7, 3), (10, 3)]
-GUARD = 4096   # bytes
 R_, F_, K_ = 7, 3, 0.45
 
 
@@ -70,11 +69,10 @@ def test_halves_of_generator_films(built, w, h, r, f):
 
 @pytest.mark.parametrize("w,h", [(67, 45), (160, 96)], ids=["67x45", "160x96"])
 def test_block_lists(built, w, h):
-    from test_guide_emu import block_lists
     even, odd = D.random_films(w, h, seed=3 * w + h)
     full = halves_guarded(even, odd, R_, F_, K_)
     bx, by = G.blocks_of(w, h)
-    for which, blocks in block_lists(w, h).items():
+    for which, blocks in G.block_lists(w, h).items():
         got = halves_guarded(even, odd, R_, F_, K_, blocks=blocks, fill=0x5A)
         mask = G.block_mask([b for b in blocks if b < bx * by], w, h)   # (an index outside the frame's blocks is passed over)
         for g, want in zip(got, full):
@@ -84,12 +82,12 @@ def test_block_lists(built, w, h):
 
 def test_emulation_and_gpu_bits(built):
     """a finding, not a requirement: with tr::ref_expf on both sides and IEEE division the host emulation is expected to give the GPU's bits"""
-    import test_guide_emu as EM
+    import _emu_features as EF   # (builds the emulation of the guide kernels when called, here only)
     even, odd = D.random_films(67, 45, seed=5)
-    emu = EM._guide_lib()
+    emu = EF.guide_lib()
     for r, f in RF:
         gpu = halves_guarded(even, odd, r, f, 0.45)
-        cpu = EM.run_halves(emu, even, odd, r, f, 0.45)
+        cpu = EF.guide_halves(emu, even, odd, r, f, 0.45)
         for name, g, c in (("fa", gpu[0], cpu[0]), ("fb", gpu[1], cpu[1])):
             n = int((g.view(np.uint32) != c.view(np.uint32)).sum())
             print(f"r={r} f={f} {name}: {n} of {g.size} words differ between the host emulation and the GPU (max abs {np.abs(g - c).max():.3e})")

@@ -7,35 +7,16 @@ with per-path evaluation, an AnimatedMesh through the sampler pass, and Whitted.
 with a real threshold the film is the oracle's film of exactly each tile's [0, n_t), and the reported errors are the header's metric of the
 returned films."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 
 import tray_rust_amd as T
 from tray_rust_amd import scenes
-import _oracle as O
-from test_noise_target_emu import assert_ulps, numpy_tile_error
+from _noise_ref import (assert_close, assert_ulps, device_film, load, numpy_tile_error, oracle_film, pixels_in_image, queue, rmse, size,
+                        spheres_in_the_dark)
 
 pytestmark = pytest.mark.gpu
-
-
-def rgb(img):
-    return img[..., :3] / np.maximum(img[..., 3:], 1e-20)
-
-
-def rmse(a, b):
-    return float(np.sqrt(np.mean((rgb(a) - rgb(b)) ** 2)))
-
-
-def size(scene, frame):
-    film = scene.flatten(frame).contents.film
-    return film.width, film.height
-
-
-def queue(scene, frame):
-    return np.array(T.BlockQueue(size(scene, frame), (8, 8)).blocks, np.uint32).reshape(-1, 2)
 
 
 def noise_target(scene, hip, frame, min_spp, max_spp, threshold):
@@ -54,39 +35,6 @@ def noise_target(scene, hip, frame, min_spp, max_spp, threshold):
                                                     err.ctypes.data_as(C.POINTER(C.c_float)), None))
     torch.cuda.synchronize()
     return even.cpu().numpy().reshape(h, w, 4), odd.cpu().numpy().reshape(h, w, 4), smp, err, hip.timing(scene)
-
-
-def device_film(scene, hip, frame, spp, rng=None):
-    """one launch into a zeroed device film: the samples rng of every tile (rng None: tray_render_tiles_device)"""
-    import torch
-    w, h = size(scene, frame)
-    film = torch.zeros(w * h * 4, dtype=torch.float32, device="cuda:0")
-    if rng is None:
-        hip.render_device(scene, frame, (0, 0), spp, film.data_ptr())
-    else:
-        hip.render_samples_device(scene, frame, (0, 0), spp, rng, film.data_ptr())
-    torch.cuda.synchronize()
-    return film.cpu().numpy().reshape(h, w, 4)
-
-
-def pixels_in_image(scene, frame, q):
-    w, h = size(scene, frame)
-    return np.array([min(8, w - 8 * int(x)) * min(8, h - 8 * int(y)) for x, y in q], np.int64)
-
-
-def assert_close(got, want, what):
-    scale = max(1.0, float(np.abs(want).max()))
-    d = float(np.abs(got - want).max())
-    print(f"{what}: max difference {d:.2e} (bar {2e-5 * scale:.2e})")
-    assert d <= 2e-5 * scale, what
-
-
-def load(d, tmp_path, name="s.json"):
-    scenes.write_assets(str(tmp_path))
-    p = os.path.join(str(tmp_path), name)
-    with open(p, "w") as f:
-        json.dump(d, f)
-    return T.Scene.load_file(p)
 
 
 def check_threshold_zero(scene, frame, min_spp, max_spp, seed, what, hip_setup=None):
@@ -148,16 +96,6 @@ def test_huge_threshold_stops_every_tile_at_min_spp(tmp_path):
     assert_close(even, device_film(scene, hip, 0, 64, (0, 4)), "even film against [0, 4)")
 
 
-def spheres_in_the_dark(width, height, samples):
-    """smallpt without its walls: two spheres under the sphere light, the rest of the frame sees nothing"""
-    d = scenes.smallpt(width, height, samples)
-    d["objects"] = [o for o in d["objects"] if o["name"] != "walls"]
-    for o in d["objects"]:
-        if o["name"] == "metal_sphere":
-            o["material"] = "white_wall"
-    return d
-
-
 def test_background_tiles_stop_at_min_spp(tmp_path):
     """tiles farther than the filter radius from any geometry see radiance 0 in both films: error 0, so they stop after round 0; tiles on the
     lit spheres are noisy and take more samples"""
@@ -176,22 +114,6 @@ def test_background_tiles_stop_at_min_spp(tmp_path):
     assert tim.samples == int((64 * smp.astype(np.int64)).sum())
     # every lit tile that stopped early did so below the threshold
     assert (err[smp < 128] < 0.05).all()
-
-
-def oracle_film(flat, q, n_t, spp, seed):
-    """the oracle's RenderTarget::write of the samples [0, n_t[i]) of every pixel of tile q[i] (a spp-sample frame)"""
-    fs = flat.contents
-    w, h = fs.film.width, fs.film.height
-    r = 6
-    ref = np.zeros((h + 2 * r, w + 2 * r, 4), np.float32)
-    for tile, n in zip(q, n_t):
-        n = int(n)
-        px, py = np.meshgrid(np.arange(8) + 8 * int(tile[0]), np.arange(8) + 8 * int(tile[1]))
-        out = O.sample_radiance(flat, np.repeat(px.ravel(), n), np.repeat(py.ravel(), n), np.tile(np.arange(n), 64), spp, seed=seed)
-        patches = O.film_patches(fs.film, (int(tile[0]), int(tile[1])), np.concatenate([out[:, 3:5], out[:, 0:3]], 1), r)
-        for (x, y), p in zip(np.floor(out[:, 3:5]).astype(int), patches):
-            ref[y:y + 2 * r + 1, x:x + 2 * r + 1] += p
-    return ref[r:r + h, r:r + w]
 
 
 @pytest.mark.parametrize("dims", [(16, 16), (24, 16)], ids=["16x16", "24x16"])

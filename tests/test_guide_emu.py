@@ -6,80 +6,37 @@ output bit for bit; with a block list, the listed blocks equal to the full run b
 numpy's. Then the rounds of tray_render_noise_target_filtered_device on films of the oracle, driven from Python over the emulated kernels: errors
 within 4 ulps of the numpy metric of the emulated halves, flags and lists exact, n_t the numpy rule's at thresholds no tile's f64 error lies
 within 1e-3 relative of, and the property the rule rests on: at 32 samples at least 90 % of the tiles have a smaller filtered than raw error."""
-import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import tray_rust_amd as T
 from tray_rust_amd import scenes
-import _emu as E
 import _denoise_ref as D
+import _emu_features as EF
 import _guide_ref as G
-import test_denoise_emu as DE
-import test_noise_target_emu as NE
+import _noise_ref as N
+import _ranges as R
+from _emu_features import SENTINEL, guide_halves as run_halves
 
 F32 = np.float32
-GUARD = 64
-SENTINEL = np.uint32(0xDEADBEEF)
-
-
-def _guide_lib():
-    so = os.path.join(E.EMU_DIR, "libtrayemu_guide.so")
-    src = os.path.join(E.EMU_DIR, "emu_guide.cpp")
-    deps = [src, os.path.join(E.EMU_DIR, "hip_emu.h")] + [os.path.join(E.HIP_DIR, h) for h in ("guide_kernels.h", "denoise_kernels.h", "dev_libm.h")]
-    if E._stale(so, deps):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-attributes", "-shared", "-o", so, src], check=True)
-    h = C.CDLL(so)
-    h.emu_guide_halves.restype = C.c_int
-    h.emu_guide_halves.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]
-    h.emu_guide_mark.restype = C.c_int
-    h.emu_guide_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    h.emu_guide_compact.restype = C.c_int
-    h.emu_guide_compact.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    return h
 
 
 @pytest.fixture(scope="module")
 def guide():
-    return _guide_lib()
+    return EF.guide_lib()
 
 
 @pytest.fixture(scope="module")
 def denoise():
-    return DE._denoise_lib()
+    return EF.denoise_lib()
 
 
 @pytest.fixture(scope="module")
 def noise():
-    return NE._noise_lib()
-
-
-def run_halves(guide, even, odd, r, f, k, blocks=None, into=None):
-    """the launches of one tray_denoise_halves_device call in the emulation; fa, fb and the scratch buffer lie between guard words. `into`: the
-    (fa, fb) the call writes into (a block list leaves the other pixels alone); default sentinel words. Returns (fa, fb) as (h, w, 4)."""
-    even, odd = np.ascontiguousarray(even, F32), np.ascontiguousarray(odd, F32)
-    h, w = even.shape[:2]
-    outs = []
-    for i in range(2):
-        buf = np.full(h * w * 4 + 2 * GUARD, SENTINEL, np.uint32)
-        if into is not None:
-            buf[GUARD:-GUARD] = into[i].reshape(-1).view(np.uint32)
-        outs.append(buf)
-    scratch = np.full(w * h * 48 + 2 * GUARD, 0xA5, np.uint8)
-    bl = None if blocks is None else np.ascontiguousarray(blocks, np.uint32)
-    keep = bl if bl is None or len(bl) else np.zeros(1, np.uint32)   # (an empty list is still a non-null pointer)
-    rc = guide.emu_guide_halves(even.ctypes.data, odd.ctypes.data, w, h, r, f, k, None if bl is None else keep.ctypes.data, 0 if bl is None else len(bl),
-                                outs[0][GUARD:].ctypes.data, outs[1][GUARD:].ctypes.data, scratch[GUARD:].ctypes.data)
-    assert rc == 0, rc
-    for buf in outs:
-        assert (buf[:GUARD] == SENTINEL).all() and (buf[-GUARD:] == SENTINEL).all(), "a write outside fa / fb"
-    assert (scratch[:GUARD] == 0xA5).all() and (scratch[-GUARD:] == 0xA5).all(), "a write outside the scratch buffer"
-    return tuple(buf[GUARD:-GUARD].view(F32).reshape(h, w, 4).copy() for buf in outs)
+    return EF.noise_lib()
 
 
 SIZES = [(67, 45), (160, 96)]
@@ -93,18 +50,9 @@ def test_halves_match_the_f64_statement_and_average_to_the_filter(guide, denoise
     fa, fb = run_halves(guide, even, odd, r, f, 0.45)
     G.assert_halves_match(fa, fb, even, odd, r, f, 0.45, f"{w}x{h} r={r} f={f}")
     assert (fa[..., 3] == 0).any() or (fb[..., 3] == 0).any() or f > 0   # (patch 0: an invalid pixel has no partner and no weight)
-    out = DE.run(denoise, even, odd, r, f, 0.45)
+    out = EF.denoise(denoise, even, odd, r, f, 0.45)
     mean = ((fa[..., :3] + fb[..., :3]) * F32(0.5)).astype(F32)
     assert (mean.view(np.uint32) == out[..., :3].view(np.uint32)).all(), "(fa + fb) * 0.5 is not k_dn_filter's output to the bit"
-
-
-def block_lists(w, h):
-    bx, by = G.blocks_of(w, h)
-    n = bx * by
-    rng = np.random.default_rng(w + h)
-    last = sorted(set(range(bx - 1, n, bx)) | set(range((by - 1) * bx, n)))   # the last column and the last row
-    return {"empty": [], "last-row-and-column": last, "all": list(range(n)), "scattered": sorted(rng.choice(n, max(1, n // 3), replace=False).tolist()),
-            "unordered-with-one-outside": [n - 1, 0, n + 5]}
 
 
 @pytest.mark.parametrize("which", ["empty", "last-row-and-column", "all", "scattered", "unordered-with-one-outside"])
@@ -114,7 +62,7 @@ def test_a_block_list_computes_the_listed_blocks_only(guide, w, h, which):
     even, odd = D.random_films(w, h, seed=3 * w + h)
     r, f = 7, 3
     full = run_halves(guide, even, odd, r, f, 0.45)
-    blocks = block_lists(w, h)[which]
+    blocks = G.block_lists(w, h)[which]
     got = run_halves(guide, even, odd, r, f, 0.45, blocks=blocks)
     bx, by = G.blocks_of(w, h)
     mask = G.block_mask([b for b in blocks if b < bx * by], w, h)
@@ -143,7 +91,7 @@ def run_block_list(guide, queue, active, w, h):
 
 @pytest.mark.parametrize("w,h", SIZES + [(1920, 1080)], ids=[f"{w}x{h}" for w, h in SIZES + [(1920, 1080)]])
 def test_block_lists_are_numpys(guide, w, h):
-    queue = NE.tiles_over(w, h)
+    queue = N.tiles_over(w, h)
     rng = np.random.default_rng(w)
     rng.shuffle(queue)   # (the library's queue is in Morton order: any order must do)
     n = len(queue)
@@ -182,12 +130,12 @@ def oracle_rounds(tmp_path_factory, built):
             json.dump(getattr(scenes, name)(W, H, MAX_SPP), fh)
         scene, *_ = T.Scene.load_file(p)
         flat = scene.flatten(0)
-        queue = np.array(T.BlockQueue((W, H), (8, 8)).blocks, np.uint32).reshape(-1, 2)
+        queue = R.tile_queue(W, H)
         ranges = []   # per round: the films of the round's two ranges alone
         lo, hi = 0, MIN_SPP
         while hi <= MAX_SPP:
             mid = lo + (hi - lo) // 2
-            ranges.append((hi, DE.oracle_range(flat, (lo, mid), MAX_SPP, SEED), DE.oracle_range(flat, (mid, hi), MAX_SPP, SEED)))
+            ranges.append((hi,) + tuple(R.oracle_range(flat, queue, rng, MAX_SPP, SEED)[0] for rng in ((lo, mid), (mid, hi))))
             lo, hi = hi, hi * 2
         out[name] = (queue, ranges)
     return out
@@ -222,9 +170,9 @@ def drive_rounds(guide, noise, queue, ranges, threshold):
         assert m[bm].sum() == m.sum(), "an active tile outside the listed blocks"
         assert all((a.view(np.uint32)[bm] == b.view(np.uint32)[bm]).all() for a, b in ((fa, whole[0]), (fb, whole[1])))
         full = len(sel) == n
-        e_, a_, s_ = NE.run_error(noise, fa, fb, queue[sel], None if full else sel, hi, MAX_SPP, threshold, n)
+        e_, a_, s_ = EF.noise_error(noise, fa, fb, queue[sel], None if full else sel, hi, MAX_SPP, threshold, n)
         want = np.array([G.tile_error(fa, fb, t) for t in queue[sel]], F32)
-        NE.assert_ulps(e_[sel], want, 4, f"round to {hi}")
+        N.assert_ulps(e_[sel], want, 4, f"round to {hi}")
         with np.errstate(invalid="ignore"):
             assert (a_[sel] == ((~(e_[sel] < threshold)) & (hi < MAX_SPP)).astype(np.uint32)).all()
         assert (s_[sel] == hi).all()
@@ -283,7 +231,7 @@ def test_the_filtered_error_is_below_the_raw_one_at_32_samples(guide, oracle_rou
         if hi == 32:
             break
     fa, fb = run_halves(guide, even, odd, R_, F_, K_)
-    raw = np.array([NE.numpy_tile_error(even, odd, t) for t in queue])
+    raw = np.array([N.numpy_tile_error(even, odd, t) for t in queue])
     filt = np.array([G.tile_error(fa, fb, t) for t in queue])
     share = float((filt < raw).mean())
     print(f"{name} at n_t = 32: raw tile error median / max {np.median(raw):.3f} / {raw.max():.3f}, filtered {np.median(filt):.3f} / {filt.max():.3f}, "

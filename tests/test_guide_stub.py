@@ -1,19 +1,13 @@
 """tray_denoise_halves_device and tray_render_noise_target_filtered_device through the real library against the stand-in runtime
-(tests/stubs/fakehip_guide.c: fakehip_denoise.c plus one log line per launch of libtrayhip_guide.so), as tests/test_denoise_stub.py: every
+(tests/stubs/fakehip.c: one log line per launch of libtrayhip_guide.so), as tests/test_denoise_stub.py: every
 TRAY_E_INVALID case of include/trayhip.h for both calls, the scratch size, the launches of a halves call, round 0's launch sequence of the
 filtered rule (the stand-in block compaction answers "every block", the stand-in tile compaction "no tile": the call ends after round 0), and
 tray_render_noise_target_device / tray_denoise_device launching exactly what they launched before."""
 import os
-import subprocess
-import sys
 
-import pytest
-
-from test_noise_target_stub import events as noise_events, kv
-from test_denoise_stub import denoise_events
+from _stub import events as all_events, stub   # (stub: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUBS = os.path.join(ROOT, "tests", "stubs")
 
 DRIVER = r'''
 import ctypes as C, os, sys
@@ -98,39 +92,10 @@ print("DONE")
 '''
 
 
-@pytest.fixture(scope="module")
-def stub(tmp_path_factory, built):
-    d = tmp_path_factory.mktemp("guide_stub")
-    hip = str(d / "libfakehip_guide.so")
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", hip, os.path.join(STUBS, "fakehip_guide.c"), "-lpthread", "-ldl"], check=True)
-    return hip
-
-
 def run(stub, tmp_path, mode):
-    log = str(tmp_path / "calls.log")
-    env = dict(os.environ, LD_PRELOAD=stub, FAKEHIP_LOG=log, FAKEHIP_DEVICES="1", FAKEHIP_TILE_KERNEL="1")
-    out = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "tmp": str(tmp_path), "mode": mode}], env=env, capture_output=True, text=True,
-                         timeout=300)
+    out, log = stub(DRIVER % {"root": ROOT, "tmp": str(tmp_path), "mode": mode}, tmp_path, FAKEHIP_DEVICES=1, FAKEHIP_TILE_KERNEL=1)
     assert "DONE" in out.stdout, out.stdout + out.stderr
-    return out.stdout, open(log).read().splitlines() if os.path.exists(log) else []
-
-
-def all_events(log):
-    """every launch in order: the tile kernels and the noise library's as test_noise_target_stub.events has them, ("denoise", kernel, template
-    argument, grid, block, stream) and ("guide", kernel, template argument or -1, grid, block, stream)"""
-    out = []
-    for i, l in enumerate(log):
-        if l.startswith(("range", "noise")):
-            out += noise_events(log[i:i + 1] + [m for m in log[i + 1:] if m.startswith("launch")][:1])
-        elif l.startswith("denoise"):
-            out += [("denoise",) + e for e in denoise_events([l])]
-        elif l.startswith("guide"):
-            n = kv(l)
-            sym = n["kernel"]
-            name = next((k for k in ("k_dn_filter_halves", "k_guide_mark", "k_guide_compact") if k in sym), sym)
-            arg = int(sym.split("ILi", 1)[1].split("E", 1)[0]) if "ILi" in sym else -1
-            out.append(("guide", name, arg, int(n["grid"]), int(n["block"]), n["stream"]))
-    return out
+    return out.stdout, log
 
 
 PX = lambda w, h: (w * h + 255) // 256

@@ -5,13 +5,12 @@ kernels do nothing, hipMemGetInfo reports FAKEHIP_FREE_BYTES, hipMalloc refuses 
 The expected numbers of sequences b - e were recorded from the library before its launch buffers had one owner (device_api.hip: LaunchBuffers)."""
 import json
 import os
-import subprocess
-import sys
 
 import pytest
 
+from _stub import stub   # (a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUBS = os.path.join(ROOT, "tests", "stubs")
 TR_XF_REC = 32   # floats per record of the cache and the table (dev_anim.h)
 KEYS = ("pool_slots", "xf_cache_bytes", "xf_table_bytes", "transform_table")
 
@@ -89,21 +88,13 @@ EXPECTED = {
 }
 
 
-@pytest.fixture(scope="module")
-def fakehip(tmp_path_factory):
-    d = tmp_path_factory.mktemp("stubs")
-    hip = str(d / "libfakehip.so")
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", hip, os.path.join(STUBS, "fakehip.c"), "-lpthread"], check=True)
-    return hip
-
-
-def run(fakehip, tmp_path, seq):
-    env = dict(os.environ, LD_PRELOAD=fakehip, FAKEHIP_DEVICES="1", FAKEHIP_WF_DONE="1", FAKEHIP_FREE_BYTES=str(4 << 30), TRAYHIP_MODE="wave")
+def run(stub, tmp_path, seq):
+    env = dict(FAKEHIP_DEVICES=1, FAKEHIP_WF_DONE=1, FAKEHIP_FREE_BYTES=4 << 30, TRAYHIP_MODE="wave")
     for k in ("TRAYHIP_WF_SLOTS", "TRAYHIP_XF_TABLE", "TRAYHIP_XF_CACHE_BYTES", "FAKEHIP_MALLOC_MAX", "FAKEHIP_LOG", "FAKEHIP_TILE_KERNEL"):
-        env.pop(k, None)
+        env[k] = None   # (not inherited)
     env.update(ENV[seq])
     steps = "\n".join("    " + s for s in STEPS[seq])
-    out = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "tmp": str(tmp_path), "size": 128 if seq == "e" else 64, "steps": steps}], env=env, capture_output=True, text=True, timeout=300)
+    out, _ = stub(DRIVER % {"root": ROOT, "tmp": str(tmp_path), "size": 128 if seq == "e" else 64, "steps": steps}, tmp_path, **env)
     assert "DONE" in out.stdout, out.stdout + out.stderr
     return [(l.split()[1], json.loads(l.split(None, 2)[2])) for l in out.stdout.splitlines() if l.startswith("STEP")]
 
@@ -113,8 +104,8 @@ def numbers(steps):
 
 
 @pytest.mark.parametrize("seq", sorted(STEPS))
-def test_launch_buffers_through_the_abi(fakehip, tmp_path, seq, built):
-    steps = run(fakehip, tmp_path, seq)
+def test_launch_buffers_through_the_abi(stub, tmp_path, seq, built):
+    steps = run(stub, tmp_path, seq)
     for label, sch in steps:
         # the bound that keeps the stage kernels inside the per-path cache: a wavefront launch that evaluates per path has a cache for every pool slot
         if sch["launched_wavefront"] and not sch["transform_table"]:

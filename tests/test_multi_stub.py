@@ -6,13 +6,12 @@ nothing but log their arguments and leave a mark per device in the film, the sta
 plumbing (which device is current at every call, shard arguments, group pairing, counts, root, error path), not pixels."""
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
+from _stub import stub_rccl   # (a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUBS = os.path.join(ROOT, "tests", "stubs")
 
 DRIVER = r'''
 import ctypes as C, os, sys
@@ -44,29 +43,14 @@ print("DONE")
 '''
 
 
-@pytest.fixture(scope="module")
-def stubs(tmp_path_factory):
-    d = tmp_path_factory.mktemp("stubs")
-    hip = str(d / "libfakehip.so")
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", hip, os.path.join(STUBS, "fakehip.c"), "-lpthread"], check=True)
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", str(d / "librccl.so"), os.path.join(STUBS, "fakerccl.c"), "-ldl"], check=True)
-    return d, hip
-
-
-def run(stubs, tmp_path, n_dev, fail=None, w=64, h=48):
-    d, hip = stubs
-    log = str(tmp_path / "calls.log")
-    env = dict(os.environ, LD_PRELOAD=hip, LD_LIBRARY_PATH=str(d) + ":" + os.environ.get("LD_LIBRARY_PATH", ""), FAKEHIP_LOG=log,
-               FAKEHIP_DEVICES=str(n_dev), FAKEHIP_TILE_KERNEL="1")
-    if fail:
-        env["FAKERCCL_FAIL"] = fail
-    out = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "tmp": str(tmp_path), "w": w, "h": h}], env=env, capture_output=True, text=True, timeout=300)
-    return out, open(log).read().splitlines() if os.path.exists(log) else []
+def run(stub_rccl, tmp_path, n_dev, fail=None, w=64, h=48):
+    return stub_rccl(DRIVER % {"root": ROOT, "tmp": str(tmp_path), "w": w, "h": h}, tmp_path, FAKEHIP_DEVICES=n_dev, FAKEHIP_TILE_KERNEL=1,
+                     FAKERCCL_FAIL=fail)
 
 
 @pytest.mark.parametrize("n_dev,w,h", [(2, 64, 48), (8, 256, 128), (8, 64, 48)])   # the last: 48 tiles = 3 chunks of 16 on 8 devices, five shards are empty
-def test_in_process_multi_device_path_against_stub_runtimes(stubs, tmp_path, n_dev, w, h, built):
-    out, log = run(stubs, tmp_path, n_dev, w=w, h=h)
+def test_in_process_multi_device_path_against_stub_runtimes(stub_rccl, tmp_path, n_dev, w, h, built):
+    out, log = run(stub_rccl, tmp_path, n_dev, w=w, h=h)
     assert "DONE" in out.stdout, out.stdout + out.stderr
     renders = [l for l in out.stdout.splitlines() if l.startswith("RENDER_OK")]
     assert len(renders) == 2, out.stdout + out.stderr
@@ -104,8 +88,8 @@ def test_in_process_multi_device_path_against_stub_runtimes(stubs, tmp_path, n_d
     assert sum(1 for l in log if l.startswith("nccl_comm_destroy")) == n_dev
 
 
-def test_a_failing_collective_is_reported_and_the_current_device_restored(stubs, tmp_path, built):
-    out, log = run(stubs, tmp_path, 2, fail="reduce")
+def test_a_failing_collective_is_reported_and_the_current_device_restored(stub_rccl, tmp_path, built):
+    out, log = run(stub_rccl, tmp_path, 2, fail="reduce")
     assert "TRAY_ERROR -5" in out.stdout and "ncclReduce failed" in out.stdout, out.stdout + out.stderr   # TRAY_E_DEVICE
     assert re.search(r"CURRENT_DEVICE 0 1\b", out.stdout), out.stdout
     assert any(l.startswith("nccl_group_end") for l in log)                                  # the group is closed even when a reduce failed

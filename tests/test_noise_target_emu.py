@@ -6,65 +6,30 @@ barriers of the block-wide scan execute as on the device. Bars: errors within 4 
 samples exact, the compacted list exactly the flagged queue entries in queue order. The rounds after the first render a list of the tiles
 that are still active; the range launches of every schedule must render exactly those tiles' samples, with the bars of
 tests/test_sample_ranges_emu.py."""
-import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import tray_rust_amd as T
 from tray_rust_amd import scenes
-import _emu as E
-import test_sample_ranges_emu as R   # (the range entry points of the emulation and the oracle's film of a range: render_range, oracle_range)
+import _emu_features as EF
+import _ranges as R   # (the oracle's film of a range and its bars)
+from _emu_features import noise_error as run_error
+from _noise_ref import assert_ulps, numpy_tile_error, tiles_over
 
-NOISE_HDR = os.path.join(E.HIP_DIR, "noise_kernels.h")
 F32 = np.float32
-
-
-def _noise_lib():
-    so = os.path.join(E.EMU_DIR, "libtrayemu_noise.so")
-    src = os.path.join(E.EMU_DIR, "emu_noise.cpp")
-    if E._stale(so, [src, os.path.join(E.EMU_DIR, "hip_emu.h"), NOISE_HDR]):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-attributes", "-shared", "-o", so, src], check=True)
-    h = C.CDLL(so)
-    h.emu_noise_error.restype = C.c_int
-    h.emu_noise_error.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]
-    h.emu_noise_compact.restype = C.c_int
-    h.emu_noise_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-    return h
 
 
 @pytest.fixture(scope="module")
 def noise():
-    return _noise_lib()
+    return EF.noise_lib()
 
 
-def numpy_tile_error(even, odd, tile):
-    """include/trayhip.h's error of one tile, in float32 and in the header's order of operations"""
-    tx, ty = int(tile[0]), int(tile[1])
-    E_ = even[8 * ty:8 * ty + 8, 8 * tx:8 * tx + 8].reshape(-1, 4)   # (the slice keeps the pixels inside the image)
-    O_ = odd[8 * ty:8 * ty + 8, 8 * tx:8 * tx + 8].reshape(-1, 4)
-    with np.errstate(all="ignore"):
-        e, o = E_[:, :3] / E_[:, 3:], O_[:, :3] / O_[:, 3:]
-        d = ((np.abs(e[:, 0] - o[:, 0]) + np.abs(e[:, 1] - o[:, 1])) + np.abs(e[:, 2] - o[:, 2])) * F32(0.5)
-        s = (((e[:, 0] + e[:, 1]) + e[:, 2]) + ((o[:, 0] + o[:, 1]) + o[:, 2])) * F32(0.5)
-        m = np.where(s > 0, s, F32(0))
-        err = (d / (F32(1e-4) + np.sqrt(m))).astype(F32)
-    err = np.where((E_[:, 3] <= 0) | (O_[:, 3] <= 0), F32(np.inf), err)
-    return F32(np.max(err))   # (NaN if any pixel's is)
-
-
-def assert_ulps(got, want, n_ulps, what):
-    got, want = np.asarray(got, F32), np.asarray(want, F32)
-    nan_g, nan_w = np.isnan(got), np.isnan(want)
-    assert (nan_g == nan_w).all(), f"{what}: NaN at {np.argwhere(nan_g != nan_w).ravel()[:8].tolist()}"
-    ok = ~nan_w
-    assert (got[ok] >= 0).all() and (want[ok] >= 0).all()
-    diff = np.abs(got[ok].view(np.int32).astype(np.int64) - want[ok].view(np.int32).astype(np.int64))   # (non-negative floats: bits are ordered)
-    assert diff.max(initial=0) <= n_ulps, f"{what}: {diff.max()} ulps at {np.argwhere(ok).ravel()[np.argmax(diff)]}: {got[ok][np.argmax(diff)]} vs {want[ok][np.argmax(diff)]}"
+@pytest.fixture(scope="module")
+def emu_ranges(built):
+    return EF.ranges_lib()
 
 
 def random_films(w, h, seed):
@@ -87,25 +52,6 @@ def random_films(w, h, seed):
     ys, xs = pick(4); odd[ys, xs] = even[ys, xs]   # both halves agree: d = 0
     ys, xs = pick(3); even[ys, xs, :3] *= -1.0; odd[ys, xs, :3] *= -1.0   # negative colours: m clamps to 0
     return np.ascontiguousarray(even), np.ascontiguousarray(odd)
-
-
-def tiles_over(w, h):
-    """every 8 x 8 tile that covers part of a w x h image, row by row (BlockQueue refuses sizes that are not multiples of 8; the error kernel
-    takes any list and clips to the image)"""
-    return np.array([(x, y) for y in range((h + 7) // 8) for x in range((w + 7) // 8)], np.uint32).reshape(-1, 2)
-
-
-def run_error(noise, even, odd, tiles, qidx, n_taken, max_spp, threshold, n_queue):
-    h, w = even.shape[:2]
-    tiles = np.ascontiguousarray(tiles, np.uint32)
-    err = np.full(n_queue, -1.0, F32)
-    active = np.full(n_queue, 7, np.uint32)
-    samples = np.full(n_queue, 7, np.uint32)
-    q = None if qidx is None else np.ascontiguousarray(qidx, np.uint32)
-    rc = noise.emu_noise_error(even.ctypes.data, odd.ctypes.data, w, h, tiles.ctypes.data, None if q is None else q.ctypes.data, len(tiles), n_taken,
-                               max_spp, threshold, err.ctypes.data, active.ctypes.data, samples.ctypes.data)
-    assert rc == 0
-    return err, active, samples
 
 
 @pytest.mark.parametrize("w,h", [(20, 12), (40, 24), (64, 64)], ids=["20x12-edge-tiles", "40x24", "64x64"])
@@ -211,7 +157,7 @@ def test_range_launches_over_a_scattered_tile_list(case, cornell_list, emu_range
     _, flat, q, refs = cornell_list
     assert len(q) == 3 and not (np.diff(np.arange(8)[SCATTER]) == 1).any()
     for rng in LIST_RANGES:
-        img, counts = R.render_range(emu_ranges, kind, flat, q, rng, **kw)
+        img, counts = EF.render_range(emu_ranges, kind, flat, q, rng, **kw)
         ref, ref_counts = refs[rng]
         assert counts == ref_counts and counts[0] == len(q) * 64 * (rng[1] - rng[0]), (rng, counts, ref_counts)
         R.assert_film_matches(img, ref, f"{kind} {env} list {q.tolist()} range {rng}")
@@ -220,12 +166,8 @@ def test_range_launches_over_a_scattered_tile_list(case, cornell_list, emu_range
 def test_sampler_pass_over_a_scattered_tile_list(flag_list, emu_ranges):
     _, flat, q, refs = flag_list
     for rng in LIST_RANGES:
-        img, counts = R.render_range(emu_ranges, "sampler", flat, q, rng)
+        img, counts = EF.render_range(emu_ranges, "sampler", flat, q, rng)
         ref, ref_counts = refs[rng]
         assert counts == ref_counts, (rng, counts, ref_counts)
         R.assert_film_matches(img, ref, f"sampler pass list {q.tolist()} range {rng}")
 
-
-@pytest.fixture(scope="module")
-def emu_ranges(built):
-    return R._lib()

@@ -1,16 +1,13 @@
-"""tray_render_noise_target_device through the real library against the stand-in runtime (tests/stubs/fakehip_noise.c: fakehip.c plus a log
-line of the sample range every tile kernel receives and one of every launch of libtrayhip_noise.so), as tests/test_sample_ranges_stub.py: the
+"""tray_render_noise_target_device through the real library against the stand-in runtime (tests/stubs/fakehip.c: a log line of the
+sample range every tile kernel receives and one of every launch of libtrayhip_noise.so), as tests/test_sample_ranges_stub.py: the
 argument checks, round 0's two range launches over the whole tile range followed by the error and compaction kernels, and a plain
 tray_render_tiles_device that launches what it launched before. The stand-in kernels do nothing, so the compacted list is empty after round 0
 and the call ends there."""
 import os
-import subprocess
-import sys
 
-import pytest
+from _stub import events, stub   # (stub: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUBS = os.path.join(ROOT, "tests", "stubs")
 
 DRIVER = r'''
 import ctypes as C, os, sys
@@ -56,42 +53,10 @@ print("DONE")
 '''
 
 
-@pytest.fixture(scope="module")
-def stub(tmp_path_factory, built):
-    d = tmp_path_factory.mktemp("noise_stub")
-    hip = str(d / "libfakehip_noise.so")
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", hip, os.path.join(STUBS, "fakehip_noise.c"), "-lpthread", "-ldl"], check=True)
-    return hip
-
-
 def run(stub, tmp_path, mode):
-    log = str(tmp_path / "calls.log")
-    env = dict(os.environ, LD_PRELOAD=stub, FAKEHIP_LOG=log, FAKEHIP_DEVICES="1", FAKEHIP_TILE_KERNEL="1")
-    out = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "tmp": str(tmp_path), "mode": mode}], env=env, capture_output=True, text=True,
-                         timeout=300)
+    out, log = stub(DRIVER % {"root": ROOT, "tmp": str(tmp_path), "mode": mode}, tmp_path, FAKEHIP_DEVICES=1, FAKEHIP_TILE_KERNEL=1)
     assert "DONE" in out.stdout, out.stdout + out.stderr
-    return out.stdout, open(log).read().splitlines() if os.path.exists(log) else []
-
-
-def kv(line):
-    return dict(p.split("=", 1) for p in line.split()[1:])
-
-
-def events(log):
-    """the launches in order: ("range", begin, end, tile_count, spp, chunk, chunk_stride) per tile kernel, ("noise", kernel, grid, block) per
-    kernel of libtrayhip_noise.so"""
-    out = []
-    for i, l in enumerate(log):
-        if l.startswith("range"):
-            r = kv(l)
-            launch = next(kv(m) for m in log[i + 1:] if m.startswith("launch"))
-            out.append(("range", int(r["begin"]), int(r["end"]), int(launch["tile_count"]), int(launch["spp"]), int(launch["chunk"]),
-                        int(launch["chunk_stride"])))
-        elif l.startswith("noise"):
-            n = kv(l)
-            out.append(("noise", "compact" if "compact" in n["kernel"] else "error" if "error" in n["kernel"] else n["kernel"], int(n["grid"]),
-                        int(n["block"])))
-    return out
+    return out.stdout, log
 
 
 def test_arguments_are_checked(stub, tmp_path):

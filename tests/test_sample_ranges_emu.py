@@ -6,106 +6,28 @@ progressive slices), the wavefront schedule (4 chunks, and TRAYHIP_WF_SLICES=4) 
 samples begin .. end - 1 of every pixel -- sample s traced as the whole frame traces it -- with the counts of those samples, and the
 films of ranges that partition [0, spp) must add up to the whole frame. Bars as tests/test_film_footprints.py: equal touched pixels,
 per-pixel weight within 2e-5 of the pixel's own."""
-import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import tray_rust_amd as T
-from tray_rust_amd import _lib as L
 from tray_rust_amd import scenes
 import _emu as E
+import _emu_features as EF
+from _emu_features import render_range
 import _oracle as O
+from _ranges import SEED, SPP, assert_film_matches, oracle_range, tile_queue
 
-SPP = 16
 RANGES = [(0, 5), (5, 13), (13, 16), (7, 8)]   # three that partition [0, 16) (none a power of two long but the middle one), and one sample
 PARTITION = RANGES[:3]
 W, H = 16, 16
-SEED = 7
-
-
-def _lib():
-    so = os.path.join(E.EMU_DIR, "libtrayemu_ranges.so")
-    src = os.path.join(E.EMU_DIR, "emu_sample_ranges.cpp")
-    _, deps, cmd = E._target(())
-    deps = deps + [src]
-    if E._stale(so, deps):
-        cmd = [so if a == cmd[cmd.index("-o") + 1] else a for a in cmd]
-        cmd[cmd.index(os.path.join(E.EMU_DIR, "emu_kernels.cpp"))] = src
-        subprocess.run(cmd, check=True)
-    h = C.CDLL(so)
-    FS = C.POINTER(L.TrayFlatScene)
-    h.emu_render_tiles_range.restype = C.c_int
-    h.emu_render_tiles_range.argtypes = [FS, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32,
-                                         C.c_int, C.c_int, C.c_void_p]
-    h.emu_render_wavefront_range.restype = C.c_int
-    h.emu_render_wavefront_range.argtypes = [FS, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32,
-                                             C.c_uint32, C.c_void_p]
-    h.emu_render_sampler_range.restype = C.c_int
-    h.emu_render_sampler_range.argtypes = [FS, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32,
-                                           C.c_void_p]
-    return h
 
 
 @pytest.fixture(scope="module")
 def emu_ranges(built):
-    return _lib()
-
-
-def tile_queue(width, height):
-    return np.array(T.BlockQueue((width, height), (8, 8)).blocks, np.uint32).reshape(-1, 2)
-
-
-def render_range(h, kind, flat, q, rng, **kw):
-    """one range launch in the emulation; returns (rgbw image, (samples, vertices, rays))"""
-    fs = flat.contents
-    img = np.zeros((fs.film.height, fs.film.width, 4), np.float32)
-    st = np.zeros(4, np.uint64)
-    q = np.ascontiguousarray(q, np.uint32)
-    if kind == "tiles":
-        rc = h.emu_render_tiles_range(flat, q.ctypes.data, len(q), SPP, rng[0], rng[1], SEED, img.ctypes.data, 2, -1, kw.get("film_rows", -1), st.ctypes.data)
-    elif kind == "wavefront":
-        rc = h.emu_render_wavefront_range(flat, q.ctypes.data, len(q), SPP, rng[0], rng[1], SEED, img.ctypes.data, 4, 2, st.ctypes.data)
-    else:
-        rc = h.emu_render_sampler_range(flat, q.ctypes.data, len(q), SPP, rng[0], rng[1], SEED, img.ctypes.data, 0, st.ctypes.data)
-    assert rc == 0, f"{kind} range {rng}: {rc}"
-    return img, tuple(int(v) for v in st[:3])
-
-
-def oracle_range(flat, q, rng):
-    """the oracle's film of the samples [begin, end) of every pixel of the tiles q: oracle_sample_radiance for the samples (clamped colour,
-    film position, vertices, rays), oracle_film_patches for RenderTarget::write of each; returns (rgbw image, (samples, vertices, rays))"""
-    fs = flat.contents
-    w, h = fs.film.width, fs.film.height
-    r = E.FILM_PATCH_R
-    pad = np.zeros((h + 2 * r, w + 2 * r, 4), np.float32)
-    counts = np.zeros(3, np.int64)
-    for tile in q:
-        px, py = np.meshgrid(np.arange(8) + 8 * int(tile[0]), np.arange(8) + 8 * int(tile[1]))
-        px, py = np.repeat(px.ravel(), rng[1] - rng[0]), np.repeat(py.ravel(), rng[1] - rng[0])
-        si = np.tile(np.arange(rng[0], rng[1]), 64)
-        out = O.sample_radiance(flat, px, py, si, SPP, seed=SEED)
-        counts += (len(out), int(out[:, 5].sum()), int(out[:, 6].sum()))
-        s = np.concatenate([out[:, 3:5], out[:, 0:3]], 1)
-        patches = O.film_patches(fs.film, (int(tile[0]), int(tile[1])), s, r)
-        for (x, y), p in zip(np.floor(out[:, 3:5]).astype(int), patches):
-            pad[y:y + 2 * r + 1, x:x + 2 * r + 1] += p   # (patch pixel (r, r) is the sample's own pixel; pad shifts by r)
-    return pad[r:r + h, r:r + w], tuple(int(c) for c in counts)
-
-
-def assert_film_matches(img, ref, what):
-    """touched pixels equal; weight per pixel within 2e-5 of the pixel's own weight (tests/test_film_footprints.py)"""
-    t_img, t_ref = img[..., 3] != 0, ref[..., 3] != 0
-    assert (t_img == t_ref).all(), f"{what}: touched pixels differ at {np.argwhere(t_img != t_ref)[:8].tolist()}"
-    wr = np.abs(img[..., 3] - ref[..., 3])[t_ref] / np.abs(ref[..., 3][t_ref])
-    assert wr.max() <= 2e-5, f"{what}: per-pixel relative weight difference {wr.max():.2e} on {int((wr > 2e-5).sum())} px"
-    full = ref[..., 3] >= 0.1 * ref[..., 3].max()
-    a = img[..., :3][full] / img[..., 3:][full]
-    b = ref[..., :3][full] / ref[..., 3:][full]
-    assert np.abs(a - b).max() < 2e-5, what
+    return EF.ranges_lib()
 
 
 @pytest.fixture(scope="module")

@@ -1,17 +1,16 @@
-"""Sample ranges through the real library against the stand-in runtimes (tests/stubs/fakehip_ranges.c -- fakehip.c plus a log line of the
-range k_path_tiles receives -- and tests/stubs/fakerccl.c), as tests/test_multi_stub.py: the argument checks of tray_render_samples_device,
+"""Sample ranges through the real library against the stand-in runtimes (tests/stubs/fakehip.c, which logs the range k_path_tiles
+receives in front of the launch, and tests/stubs/fakerccl.c), as tests/test_multi_stub.py: the argument checks of tray_render_samples_device,
 tray_multi_set_partition and tray_multi_shard_samples, the range reaching the kernel, and tray_render_frame_multi under
 TRAY_PARTITION_SAMPLES -- every device renders every tile with its own range, the ranges tile [0, spp), one grouped reduce -- while the
 default partition launches what it launched before."""
 import os
 import re
-import subprocess
-import sys
 
 import pytest
 
+from _stub import stub_rccl, tile_launches as launches   # (stub_rccl: a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUBS = os.path.join(ROOT, "tests", "stubs")
 
 DRIVER = r'''
 import ctypes as C, os, sys
@@ -57,44 +56,15 @@ print("DONE")
 '''
 
 
-@pytest.fixture(scope="module")
-def stubs(tmp_path_factory, built):
-    d = tmp_path_factory.mktemp("stubs")
-    hip = str(d / "libfakehip_ranges.so")
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", hip, os.path.join(STUBS, "fakehip_ranges.c"), "-lpthread", "-ldl"], check=True)
-    subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-o", str(d / "librccl.so"), os.path.join(STUBS, "fakerccl.c"), "-ldl"], check=True)
-    return d, hip
-
-
-def run(stubs, tmp_path, n_dev, mode, w=64, h=48, spp=16):
-    d, hip = stubs
-    log = str(tmp_path / "calls.log")
-    env = dict(os.environ, LD_PRELOAD=hip, LD_LIBRARY_PATH=str(d) + ":" + os.environ.get("LD_LIBRARY_PATH", ""), FAKEHIP_LOG=log,
-               FAKEHIP_DEVICES=str(n_dev), FAKEHIP_TILE_KERNEL="1")
-    out = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT, "tmp": str(tmp_path), "w": w, "h": h, "spp": spp, "mode": mode}], env=env,
-                         capture_output=True, text=True, timeout=300)
+def run(stub_rccl, tmp_path, n_dev, mode, w=64, h=48, spp=16):
+    out, log = stub_rccl(DRIVER % {"root": ROOT, "tmp": str(tmp_path), "w": w, "h": h, "spp": spp, "mode": mode}, tmp_path, FAKEHIP_DEVICES=n_dev,
+                         FAKEHIP_TILE_KERNEL=1)
     assert "DONE" in out.stdout, out.stdout + out.stderr
-    return out.stdout, open(log).read().splitlines() if os.path.exists(log) else []
+    return out.stdout, log
 
 
-def kv(line):
-    return dict(p.split("=") for p in line.split()[1:])
-
-
-def launches(log):
-    """(range line, launch line) pairs of the tile-kernel launches, in order: a launch's own line is the next launch line of the same device
-    (the devices' host threads log side by side)"""
-    out = []
-    for i, l in enumerate(log):
-        if l.startswith("range"):
-            r = kv(l)
-            launch = next(kv(m) for m in log[i + 1:] if m.startswith("launch") and kv(m)["dev"] == r["dev"])
-            out.append((r, launch))
-    return out
-
-
-def test_range_arguments_are_checked_and_reach_the_kernel(stubs, tmp_path):
-    out, log = run(stubs, tmp_path, 2, "errors")
+def test_range_arguments_are_checked_and_reach_the_kernel(stub_rccl, tmp_path):
+    out, log = run(stub_rccl, tmp_path, 2, "errors")
     for args in ["0 0 16 5 5", "0 0 16 6 5", "0 0 16 0 17", "0 0 12 0 4", "0 0 0 0 1"]:   # empty, reversed, past spp, spp 12, spp 0
         assert f"RANGE {args} -1" in out, out
     assert "RANGE_OK 0" in out and "UNIFORM -4" in out and "ADAPTIVE -4" in out, out
@@ -107,9 +77,9 @@ def test_range_arguments_are_checked_and_reach_the_kernel(stubs, tmp_path):
 
 
 @pytest.mark.parametrize("n_dev", [2, 3, 8])
-def test_samples_partition_renders_every_tile_with_one_range_per_device(stubs, tmp_path, n_dev):
+def test_samples_partition_renders_every_tile_with_one_range_per_device(stub_rccl, tmp_path, n_dev):
     spp = 16
-    out, log = run(stubs, tmp_path, n_dev, "samples", spp=spp)
+    out, log = run(stub_rccl, tmp_path, n_dev, "samples", spp=spp)
     for world in (2, 3, 8):
         line = next(l for l in out.splitlines() if l.startswith(f"SHARDS {world} "))
         got = [tuple(int(v) for v in m) for m in re.findall(r"\((\d+), (\d+)\)", line)]
@@ -131,8 +101,8 @@ def test_samples_partition_renders_every_tile_with_one_range_per_device(stubs, t
     assert sum(1 for l in log if l.startswith("nccl_reduce")) == n_dev
 
 
-def test_devices_with_an_empty_range_launch_nothing_but_join_the_reduce(stubs, tmp_path):
-    out, log = run(stubs, tmp_path, 8, "samples", spp=4)
+def test_devices_with_an_empty_range_launch_nothing_but_join_the_reduce(stub_rccl, tmp_path):
+    out, log = run(stub_rccl, tmp_path, 8, "samples", spp=4)
     pairs = launches(log)
     assert sorted((int(r["dev"]), int(r["begin"]), int(r["end"])) for r, _ in pairs) == [(1, 0, 1), (3, 1, 2), (5, 2, 3), (7, 3, 4)]
     assert sum(1 for l in log if l.startswith("nccl_reduce")) == 8 and sum(1 for l in log if l.startswith("nccl_group_start")) == 1
@@ -140,10 +110,10 @@ def test_devices_with_an_empty_range_launch_nothing_but_join_the_reduce(stubs, t
 
 
 @pytest.mark.parametrize("n_dev", [2, 8])
-def test_default_partition_deals_tiles_as_before(stubs, tmp_path, n_dev):
+def test_default_partition_deals_tiles_as_before(stub_rccl, tmp_path, n_dev):
     """partition="tiles" (the default): the launches of tests/test_multi_stub.py -- 16-tile chunks round-robin, one launch per device that has
     tiles -- each with the whole frame (0 / 0)"""
-    out, log = run(stubs, tmp_path, n_dev, "tiles", spp=4)
+    out, log = run(stub_rccl, tmp_path, n_dev, "tiles", spp=4)
     busy = min(n_dev, 3)   # 48 tiles = 3 chunks of 16
     pairs = launches(log)
     assert len(pairs) == busy

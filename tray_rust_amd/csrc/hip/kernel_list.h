@@ -3,10 +3,11 @@
 // core -- as ONE unit the 83 kernels took six minutes, as eight they take one on the build container's eight cores (thirteen groups now), and a change to one
 // header recompiles all of them side by side).
 //   * kernel_group.hip defines TR_INST_GROUP = g and gets the explicit instantiation DEFINITIONS of group g: device code + host stub;
-//   * kernels.hip (the host side: scene upload, launches) gets explicit instantiation DECLARATIONS of all groups (`extern template`), so its
-//     launch sites name the kernels as before and no device code is generated for them there; the host stubs resolve inside the library.
+//   * device_api.hip (the host side: scene upload, launches; it includes kernels.hip) gets explicit instantiation DECLARATIONS of all groups
+//     (`extern template`), so its launch sites name the kernels as before and no device code is generated for them there; the host stubs resolve
+//     inside the library.
 // `template __global__ decltype(k<..>) k<..>;` names the specialisation without repeating its signature.
-// The non-template kernels (k_xf_table_build / _check, k_sampler_decide, k_debug_bsdf) are compiled with kernels.hip itself.
+// The non-template kernels (k_xf_table_build / _check, k_sampler_decide, k_debug_bsdf) are compiled with device_api.hip's unit.
 // A kernel launched without an entry here fails to link (undefined host stub), it cannot silently fall out of the library.
 #pragma once
 

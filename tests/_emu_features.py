@@ -33,7 +33,7 @@ def ranges_lib():
 
 @functools.lru_cache(None)
 def noise_lib():
-    h = C.CDLL(E.build("libtrayemu_noise.so", "emu_noise.cpp", _hip("noise_kernels.h")))
+    h = C.CDLL(E.build("libtrayemu_noise.so", "emu_noise.cpp", _hip("noise_kernels.h", "block_compact.h")))
     h.emu_noise_error.restype = C.c_int
     h.emu_noise_error.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p]
@@ -54,7 +54,7 @@ def denoise_lib():
 
 @functools.lru_cache(None)
 def guide_lib():
-    h = C.CDLL(E.build("libtrayemu_guide.so", "emu_guide.cpp", _hip("guide_kernels.h", "denoise_kernels.h", "dev_libm.h")))
+    h = C.CDLL(E.build("libtrayemu_guide.so", "emu_guide.cpp", _hip("guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h") + [os.path.join(E.EMU_DIR, "emu_denoise.cpp")]))
     h.emu_guide_halves.restype = C.c_int
     h.emu_guide_halves.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]

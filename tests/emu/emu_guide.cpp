@@ -1,19 +1,12 @@
 // Host emulation of the kernels of the filtered stopping rule (tray_rust_amd/csrc/hip/guide_kernels.h): k_dn_filter_halves, k_guide_mark and
 // k_guide_compact, compiled by g++ behind hip_emu.h and run as SIMT fibers, so that the LDS staging, the barriers, the ballots and the
-// block-wide scan execute as the device executes them. Built by tests/test_guide_emu.py.
-#include "hip_emu.h"
+// block-wide scan execute as the device executes them. Built by tests/test_guide_emu.py. Includes emu_denoise.cpp for its `prepare`.
+#include "emu_denoise.cpp"
 #include "../../tray_rust_amd/csrc/hip/guide_kernels.h"
 
 #include <vector>
 
-using namespace tr_denoise;
 using namespace tr_guide;
-
-template <int F>
-static int filter_halves(const float4* scratch, uint32_t width, uint32_t height, uint32_t radius, float k, const uint32_t* blocks, uint32_t grid, float4* fa,
-                         float4* fb) {
-    return hip_emu::launch_simt(grid, DN_BLOCK, [&] { k_dn_filter_halves<F>(scratch, width, height, radius, k, blocks, fa, fb); });
-}
 
 extern "C" {
 
@@ -23,22 +16,16 @@ int emu_guide_halves(const float* even, const float* odd, uint32_t width, uint32
                      uint32_t n_blocks, float* fa, float* fb, void* scratch) {
     if (width == 0u || height == 0u || radius < 1u || radius > DN_RMAX || patch > DN_FMAX) return -2;
     if (blocks && n_blocks == 0u) return 0;
-    const float4* const e4 = reinterpret_cast<const float4*>(even);
-    const float4* const o4 = reinterpret_cast<const float4*>(odd);
     float4* const s4 = static_cast<float4*>(scratch);
     float4* const a4 = reinterpret_cast<float4*>(fa);
     float4* const b4 = reinterpret_cast<float4*>(fb);
-    const uint32_t prep = (uint32_t)(((uint64_t)width * height + DN_PREP_BLOCK - 1u) / DN_PREP_BLOCK);
-    int rc = hip_emu::launch_simt(prep, DN_PREP_BLOCK, [&] { k_dn_prepare<0>(e4, o4, width, height, s4); });
-    if (rc == 0) rc = hip_emu::launch_simt(prep, DN_PREP_BLOCK, [&] { k_dn_prepare<1>(e4, o4, width, height, s4); });
+    const int rc = prepare(reinterpret_cast<const float4*>(even), reinterpret_cast<const float4*>(odd), width, height, s4);
     if (rc != 0) return rc;
     const uint32_t grid = blocks ? n_blocks : dn_tiles_x(width) * dn_tiles_y(height);
-    switch (patch) {
-        case 0u: return filter_halves<0>(s4, width, height, radius, k, blocks, grid, a4, b4);
-        case 1u: return filter_halves<1>(s4, width, height, radius, k, blocks, grid, a4, b4);
-        case 2u: return filter_halves<2>(s4, width, height, radius, k, blocks, grid, a4, b4);
-        default: return filter_halves<3>(s4, width, height, radius, k, blocks, grid, a4, b4);
-    }
+    return dn_with_patch(patch, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        return hip_emu::launch_simt(grid, DN_BLOCK, [&] { k_dn_filter_halves<F>(s4, width, height, radius, k, blocks, a4, b4); });
+    });
 }
 
 // one k_guide_mark launch as guide.hip makes it; queue_xy: n (x, y) pairs, active: n words or null; flags: one word per block of the frame

@@ -10,11 +10,6 @@ namespace tr_denoise {
 
 uint64_t scratch_bytes(uint32_t width, uint32_t height) { return dn_scratch_bytes(width, height); }
 
-template <int F>
-static void filter(hipStream_t stream, const float4* scratch, uint32_t width, uint32_t height, uint32_t radius, float k, float4* out) {
-    hipLaunchKernelGGL(k_dn_filter<F>, dim3(dn_tiles_x(width) * dn_tiles_y(height)), dim3(DN_BLOCK), 0, stream, scratch, width, height, radius, k, out);
-}
-
 void prepare(hipStream_t stream, const float* even, const float* odd, uint32_t width, uint32_t height, void* scratch) {
     const float4* const e4 = reinterpret_cast<const float4*>(even);
     const float4* const o4 = reinterpret_cast<const float4*>(odd);
@@ -29,12 +24,10 @@ void denoise(hipStream_t stream, const float* even, const float* odd, uint32_t w
     prepare(stream, even, odd, width, height, scratch);
     const float4* const s4 = static_cast<const float4*>(scratch);
     float4* const out4 = reinterpret_cast<float4*>(out);
-    switch (patch) {
-        case 0u: filter<0>(stream, s4, width, height, radius, k, out4); break;
-        case 1u: filter<1>(stream, s4, width, height, radius, k, out4); break;
-        case 2u: filter<2>(stream, s4, width, height, radius, k, out4); break;
-        default: filter<3>(stream, s4, width, height, radius, k, out4); break;
-    }
+    dn_with_patch(patch, [&](auto f) {
+        hipLaunchKernelGGL(k_dn_filter<decltype(f)::value>, dim3(dn_tiles_x(width) * dn_tiles_y(height)), dim3(DN_BLOCK), 0, stream, s4, width, height, radius,
+                           k, out4);
+    });
 }
 
 }  // namespace tr_denoise

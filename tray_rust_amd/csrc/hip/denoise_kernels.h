@@ -1,13 +1,15 @@
 // The dual-buffer non-local-means filter of tray_denoise_device (include/trayhip.h states the filter): k_dn_prepare resolves the two films into
-// float4 records of the scratch buffer, k_dn_filter computes the output image from them. Device code only; compiled into libtrayhip_denoise.so
-// by denoise.hip, and by g++ into the host emulation (tests/emu/emu_denoise.cpp). All arithmetic is f32 and unfused (-ffp-contract=off).
+// float4 records of the scratch buffer, dn_filter_block computes the two cross-filtered halves of one tile from them, and k_dn_filter stores
+// their mean as the output image (k_dn_filter_halves of guide_kernels.h stores the halves themselves). Device code only; compiled into
+// libtrayhip_denoise.so by denoise.hip and into libtrayhip_guide.so by guide.hip, and by g++ into the host emulation (tests/emu/emu_denoise.cpp,
+// emu_guide.cpp). All arithmetic is f32 and unfused (-ffp-contract=off).
 //
 // Scratch buffer (tray_denoise_scratch_bytes = 48 bytes per pixel): three arrays of width * height float4 records,
 //   A4[p] = (a.r, a.g, a.b, valid ? 1 : 0)      a = E.rgb / E.w where valid, else 0
 //   B4[p] = (b.r, b.g, b.b, 0)                  b = O.rgb / O.w where valid, else 0
 //   V4[p] = (V.r, V.g, V.b, 0)                  the 3 x 3 mean of (a - b)^2 / 2 over the valid pixels
 //
-// k_dn_filter. A workgroup of DN_BLOCK = 512 threads (8 waves) owns a DN_TW x DN_TH = 32 x 16 tile of the output, one pixel per thread. It
+// dn_filter_block. A workgroup of DN_BLOCK = 512 threads (8 waves) owns a DN_TW x DN_TH = 32 x 16 tile of the output, one pixel per thread. It
 // stages the records of the tile and its halo of H = r + f pixels in LDS once (positions outside the image as invalid zeros: one HBM read per
 // staged pixel), then walks the (2r+1)^2 offsets o. For each offset, between two barriers each:
 //   1. t of both buffers and `pair`, once per pixel of the tile + f halo ((32 + 2f) x (16 + 2f) positions: 836 at f = 3, 1.63 per output pixel),
@@ -24,10 +26,13 @@
 // staged arrays each 32-lane half of a wave reads 32 consecutive entries of one row (contiguous bytes: conflict-free); step 1 walks rows of
 // 32 + 2f positions, so a wave's reads wrap to the next staged row once or twice, where two lanes of a group can meet on a bank (2-way at
 // worst, on those instructions only).
-// Every thread of a workgroup reaches every barrier: the loops over offsets and items have uniform bounds, and threads whose pixel lies
-// outside the image only skip the final store.
+// Barriers: dn_filter_block owns the LDS arrays and both barriers per offset, so EVERY thread of the workgroup must call it, under control flow
+// that is uniform over the workgroup. Inside it the loops over offsets and items have uniform bounds, and a thread whose pixel lies outside
+// the image runs to the end like any other (its caller skips the store). k_dn_filter calls it unconditionally; k_dn_filter_halves either
+// returns with the whole workgroup before the call (a listed block outside the frame: the test reads no per-thread value) or calls it.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #ifndef TR_DEV
 #define TR_DEV __device__ __forceinline__
 #endif
@@ -112,9 +117,14 @@ TR_DEV float dn_term(float xp, float xq, float vp, float vq, float k2) {
     return (d * d - (vp + (vp < vq ? vp : vq))) / (DN_EPS + k2 * (vp + vq));
 }
 
+// the two filtered halves of one output pixel: A = even filtered with odd's weights, B the other way round, each (rgb, 1), or zeros where no
+// weight was collected; (px, py): the pixel, which may lie outside the image (partial tiles) -- the caller stores only inside it
+struct dn_halves { float4 A, B; uint32_t px, py; };
+
+// The calling thread's pixel of tile `block` (row-major over dn_tiles_x(width) tiles per row; block < dn_tiles_x * dn_tiles_y) from the
+// records of `scratch`. Called by all DN_BLOCK threads of a workgroup together (above).
 template <int F>
-__global__ __launch_bounds__(DN_BLOCK) void k_dn_filter(const float4* __restrict__ scratch, uint32_t width, uint32_t height, uint32_t radius, float k,
-                                                        float4* __restrict__ out) {
+TR_DEV dn_halves dn_filter_block(const float4* __restrict__ scratch, uint32_t width, uint32_t height, uint32_t radius, float k, uint32_t block) {
     constexpr uint32_t EW = DN_TW + 2u * F, EH = DN_TH + 2u * F;   // the tile + f halo: where t is needed
     constexpr uint32_t N1 = (EW * EH + DN_BLOCK - 1u) / DN_BLOCK, N2 = (DN_TW * EH + DN_BLOCK - 1u) / DN_BLOCK;   // items per thread in steps 1 and 2
     __shared__ float4 s_a[DN_STAGE_MAX];   // (a.r, a.g, a.b, valid)
@@ -128,7 +138,7 @@ __global__ __launch_bounds__(DN_BLOCK) void k_dn_filter(const float4* __restrict
     const int R = (int)radius, H = R + F;
     const uint32_t SW = DN_TW + 2u * (uint32_t)H, SH = DN_TH + 2u * (uint32_t)H;   // the staged region: SW * SH <= DN_STAGE_MAX as radius <= DN_RMAX
     const uint32_t tiles_x = dn_tiles_x(width);
-    const int x0 = (int)((blockIdx.x % tiles_x) * DN_TW), y0 = (int)((blockIdx.x / tiles_x) * DN_TH);
+    const int x0 = (int)((block % tiles_x) * DN_TW), y0 = (int)((block / tiles_x) * DN_TH);
     const size_t n = (size_t)width * height;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     for (uint32_t i = tid; i < SW * SH; i += DN_BLOCK) {
@@ -212,12 +222,30 @@ __global__ __launch_bounds__(DN_BLOCK) void k_dn_filter(const float4* __restrict
                 nbr = nbr + wa * bq.x; nbg = nbg + wa * bq.y; nbb = nbb + wa * bq.z; db = db + wa;
             }
         }
-    const uint32_t px = (uint32_t)x0 + tx, py = (uint32_t)y0 + ty;
-    if (px < width && py < height) {
-        float ar = 0.0f, ag = 0.0f, ab = 0.0f, br = 0.0f, bg = 0.0f, bb = 0.0f;
-        if (da > 0.0f) { ar = nar / da; ag = nag / da; ab = nab / da; }
-        if (db > 0.0f) { br = nbr / db; bg = nbg / db; bb = nbb / db; }
-        out[(size_t)py * width + px] = make_float4((ar + br) * 0.5f, (ag + bg) * 0.5f, (ab + bb) * 0.5f, 1.0f);
+    dn_halves h = {zero, zero, (uint32_t)x0 + tx, (uint32_t)y0 + ty};
+    if (da > 0.0f) h.A = make_float4(nar / da, nag / da, nab / da, 1.0f);
+    if (db > 0.0f) h.B = make_float4(nbr / db, nbg / db, nbb / db, 1.0f);
+    return h;
+}
+
+// one workgroup per tile of the image, row by row: out = ((A + B) / 2, 1)
+template <int F>
+__global__ __launch_bounds__(DN_BLOCK) void k_dn_filter(const float4* __restrict__ scratch, uint32_t width, uint32_t height, uint32_t radius, float k,
+                                                        float4* __restrict__ out) {
+    const dn_halves h = dn_filter_block<F>(scratch, width, height, radius, k, blockIdx.x);
+    if (h.px < width && h.py < height)
+        out[(size_t)h.py * width + h.px] = make_float4((h.A.x + h.B.x) * 0.5f, (h.A.y + h.B.y) * 0.5f, (h.A.z + h.B.z) * 0.5f, 1.0f);
+}
+
+// Host side: fn(std::integral_constant<int, F>()) for the F that patch selects (0 ... DN_FMAX; the callers have checked the range), and what it
+// returns: the one place where the run-time patch radius becomes the template argument of k_dn_filter / k_dn_filter_halves.
+template <class Fn>
+inline auto dn_with_patch(uint32_t patch, Fn&& fn) {
+    switch (patch) {
+        case 0u: return fn(std::integral_constant<int, 0>());
+        case 1u: return fn(std::integral_constant<int, 1>());
+        case 2u: return fn(std::integral_constant<int, 2>());
+        default: return fn(std::integral_constant<int, 3>());
     }
 }
 

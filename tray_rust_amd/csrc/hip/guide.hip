@@ -11,12 +11,6 @@ namespace tr_guide {
 uint32_t blocks_x(uint32_t width) { return tr_denoise::dn_tiles_x(width); }
 uint32_t blocks_y(uint32_t height) { return tr_denoise::dn_tiles_y(height); }
 
-template <int F>
-static void filter_halves(hipStream_t stream, const float4* scratch, uint32_t width, uint32_t height, uint32_t radius, float k, const uint32_t* blocks,
-                          uint32_t grid, float4* fa, float4* fb) {
-    hipLaunchKernelGGL(k_dn_filter_halves<F>, dim3(grid), dim3(DN_BLOCK), 0, stream, scratch, width, height, radius, k, blocks, fa, fb);
-}
-
 uint32_t halves(hipStream_t stream, const void* scratch, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k, const uint32_t* blocks,
                 uint32_t n_blocks, float* fa, float* fb) {
     const uint32_t grid = blocks ? n_blocks : blocks_x(width) * blocks_y(height);
@@ -24,12 +18,9 @@ uint32_t halves(hipStream_t stream, const void* scratch, uint32_t width, uint32_
     const float4* const s4 = static_cast<const float4*>(scratch);
     float4* const a4 = reinterpret_cast<float4*>(fa);
     float4* const b4 = reinterpret_cast<float4*>(fb);
-    switch (patch) {
-        case 0u: filter_halves<0>(stream, s4, width, height, radius, k, blocks, grid, a4, b4); break;
-        case 1u: filter_halves<1>(stream, s4, width, height, radius, k, blocks, grid, a4, b4); break;
-        case 2u: filter_halves<2>(stream, s4, width, height, radius, k, blocks, grid, a4, b4); break;
-        default: filter_halves<3>(stream, s4, width, height, radius, k, blocks, grid, a4, b4); break;
-    }
+    dn_with_patch(patch, [&](auto f) {
+        hipLaunchKernelGGL(k_dn_filter_halves<decltype(f)::value>, dim3(grid), dim3(DN_BLOCK), 0, stream, s4, width, height, radius, k, blocks, a4, b4);
+    });
     return 1u;
 }
 

@@ -2,6 +2,7 @@
 // compaction of the next round's tile list. Device code only; compiled into libtrayhip_noise.so by noise.hip, and by g++ into the host emulation
 // (tests/emu/emu_noise.cpp).
 #pragma once
+#include "block_compact.h"
 
 namespace tr_noise {
 
@@ -53,32 +54,20 @@ __global__ __launch_bounds__(NT_ERR_BLOCK) void k_noise_error(const float4* __re
 
 // The next round's tile list: the tiles of queue[0, n) whose active flag is set, in queue order (so the tile kernel and the wavefront's chunks
 // keep the Morton order, and the list is the same in every run), each as its coordinates (out_tiles) and its queue index (out_q); their number
-// goes to *count. One workgroup walks the queue in steps of NT_COMPACT_BLOCK entries: a ballot per wave, the waves' counts through LDS.
+// goes to *count. One workgroup walks the queue in steps of NT_COMPACT_BLOCK entries (block_compact.h; the loop's bound is uniform).
 __global__ __launch_bounds__(NT_COMPACT_BLOCK) void k_noise_compact(const uint2* __restrict__ queue, const uint32_t* __restrict__ active, uint32_t n,
                                                                     uint2* __restrict__ out_tiles, uint32_t* __restrict__ out_q,
                                                                     uint32_t* __restrict__ count) {
     __shared__ uint32_t s_wave[NT_COMPACT_BLOCK / 64u];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t total = 0u;   // entries written before this step (the same in every thread)
+    uint32_t total = 0u;
     for (uint32_t i0 = 0u; i0 < n; i0 += NT_COMPACT_BLOCK) {
         const uint32_t i = i0 + threadIdx.x;
         const bool keep = i < n && active[i] != 0u;
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0u) s_wave[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t before = 0u, sum = 0u;
-        for (uint32_t k = 0u; k < NT_COMPACT_BLOCK / 64u; ++k) {
-            const uint32_t c = s_wave[k];
-            before += k < wave ? c : 0u;
-            sum += c;
-        }
+        const uint32_t o = tr::block_compact_slot<NT_COMPACT_BLOCK>(keep, total, s_wave);   // (o < n: at most one entry per queue index)
         if (keep) {
-            const uint32_t o = total + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));   // (o < n: at most one entry per queue index)
             out_tiles[o] = queue[i];
             out_q[o] = i;
         }
-        total += sum;
-        __syncthreads();   // (s_wave is rewritten by the next step)
     }
     if (threadIdx.x == 0u) *count = total;
 }

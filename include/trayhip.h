@@ -412,6 +412,37 @@ uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height);
 int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                         float* out_dev, void* scratch_dev, void* stream);
 
+/* tray_denoise_device for a frame of a sequence: the filter also searches the half films of N neighbouring frames. The sampler is keyed by the
+ * frame, so the neighbours carry independent noise over almost the same image; NL-means matches patches, so no motion vectors are needed, and
+ * where the motion is too fast for a neighbour's patches to match, its weights vanish and the frame is filtered as by tray_denoise_device.
+ * - Frames. Frame 0 is the centre pair (E_0, O_0) = (even_dev, odd_dev); frames 1 ... N are (nb_even_dev[j - 1], nb_odd_dev[j - 1]), in the
+ *   caller's order. Every frame j is resolved as above, on its own, into a_j, b_j, valid_j and V_j.
+ * - Window. q runs over p + [-radius, radius]^2 in frame 0 and over p + [-radius_t, radius_t]^2 in every frame j >= 1.
+ * - Distance of p (frame 0) and q (frame j) in buffer x: t takes the centre frame's values at p' = p + n, x_0(p') and V_0(p'), and frame j's at
+ *   q' = q + n, x_j(q') and V_j(q'); pair(n) = valid_0(p') valid_j(q') (0 outside the image);
+ *     d2_x(p, q, j) = sum_n t(p', q') pair(n) / (3 sum_n pair(n)) over the (2 patch + 1)^2 offsets n.
+ * - Weight. w_x(p, q, j) = exp(-max(0, d2_x)) if q is inside the image, valid in frame j and sum_n pair(n) > 0, else 0.
+ * - Cross filtering. A(p) = sum_j sum_q w_b(p, q, j) a_j(q) / sum_j sum_q w_b(p, q, j), B(p) likewise with w_a and b_j; a quotient whose
+ *   denominator is 0 is 0. out(p) = ((A + B) / 2, 1).
+ * - Order. The sums run over frame 0 first, then frames 1 ... N in the given order; within a frame dy outer and dx inner, ascending; f32,
+ *   unfused, IEEE division, the library's own expf. With N = 0 the output is tray_denoise_device's, bit for bit. No atomics: the same bits in
+ *   every run.
+ * - Every output channel lies between the minimum and the maximum of that channel of a_j and b_j over the valid pixels of the pixel's windows
+ *   in all frames, up to rounding.
+ * tray_denoise_temporal_scratch_bytes: 128 bytes per pixel, whatever N is (the centre's records, the current neighbour's, the sums; 0 if width
+ * or height is 0). nb_even_dev / nb_odd_dev are HOST arrays of n_neighbours device pointers, read during the call; they may be null only when
+ * n_neighbours is 0. 3 (N + 1) kernel launches on `stream` (per frame tray_denoise_device's two preparing ones and one pass over the 32 x 16
+ * tiles), asynchronous, no host synchronisation, on the current device (tray_init).
+ * Returns TRAY_E_INVALID, before any device call, under tray_denoise_device's rules for width, height, radius, patch and k, unless
+ * 1 <= radius_t <= radius and n_neighbours <= TRAY_DENOISE_MAX_NEIGHBOURS, if a film, out_dev or scratch_dev is null, or unless all 2 (N + 1)
+ * films, out_dev and scratch_dev are pairwise different buffers, 16-byte aligned. */
+#define TRAY_DENOISE_RADIUS_T 3
+#define TRAY_DENOISE_MAX_NEIGHBOURS 8
+uint64_t tray_denoise_temporal_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                 const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch,
+                                 float k, float* out_dev, void* scratch_dev, void* stream);
+
 /* The two cross-filtered halves of tray_denoise_device's statement as RGBW films: fa = (A(p), wA), fb = (B(p), wB), where wA = 1 if A's denominator
  * sum_q w_b(p, q) is > 0, else 0 (then A = 0), wB likewise. (fa.rgb + fb.rgb) * 0.5f is tray_denoise_device's out.rgb, bit for bit.
  * |fa - fb| / 2 is a per-pixel confidence map of the denoised frame: the two halves are two estimates of the same image.

@@ -433,6 +433,79 @@ class Hip:
             rt.add_pixels(out.reshape(-1).cpu().numpy())
         return result
 
+    def _denoise_temporal_device(self, centre, neighbours, radius, radius_t, patch, k):
+        """tray_denoise_temporal_device of (even, odd) pairs of (h, w, 4) float32 tensors of this device on the current stream: `centre` filtered
+        with `neighbours` (a list of pairs, in order); returns the output tensor"""
+        import torch
+        e, o = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        n = len(neighbours)
+        pointers = lambda i: (C.c_void_p * max(n, 1))(*[pair[i].data_ptr() for pair in neighbours])
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), n, pointers(0), pointers(1), int(radius),
+                                                     int(radius_t), int(patch), float(k), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                                     C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return out
+
+    def denoise_temporal(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
+                         k=_lib.TRAY_DENOISE_K):
+        """denoise() for a frame of a sequence (tray_denoise_temporal_device): `frames` is a list of (even, odd) half-film pairs of consecutive frames,
+        as denoise() takes them; frames[centre] is filtered, and its filter also searches a window of radius_t in each of the other frames, in
+        list order (at most 8 of them). Returns the same kind it was given. A one-element list gives denoise()'s image to the bit."""
+        frames = list(frames)
+        if not 0 <= int(centre) < len(frames):
+            raise ValueError("denoise_temporal: centre must index frames")
+        on_device = [self._films_on_device("denoise_temporal", even, odd) for even, odd in frames]
+        if len({kind for kind, _, _ in on_device}) != 1:
+            raise TypeError("denoise_temporal: the frames must all be numpy arrays or all be torch tensors")
+        pairs = [(e, o) for _, e, o in on_device]
+        if any(e.shape != pairs[0][0].shape for e, _ in pairs):
+            raise ValueError("denoise_temporal: the frames must be of one size")
+        out = self._denoise_temporal_device(pairs[int(centre)], pairs[:int(centre)] + pairs[int(centre) + 1:], radius, radius_t, patch, k)
+        return out.cpu().numpy() if on_device[0][0] else out
+
+    def render_sequence_denoised(self, scene, config, frames, reach=1, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
+                                 patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+        """Generator over the consecutive frame numbers `frames`: config.select_blocks of every frame rendered once as its two half films (the sample
+        ranges [0, spp / 2) and [spp / 2, spp) of the round_spp(config.spp)-sample frame, as render_denoised without a threshold) and filtered
+        with the up to `reach` frames before and after it that belong to `frames` (denoise_temporal, the neighbours in ascending frame order);
+        yields (frame, rgbw) with rgbw an (h, w, 4) numpy array of weight 1. At most 2 reach + 1 film pairs live on the device. One seed, self.seed:
+        the frame number already keys the sampler. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        import torch
+        frames, reach = [int(f) for f in frames], int(reach)
+        if any(b != a + 1 for a, b in zip(frames, frames[1:])):
+            raise ValueError("render_sequence_denoised: frames must be consecutive frame numbers")
+        if not 0 <= 2 * reach <= _lib.TRAY_DENOISE_MAX_NEIGHBOURS:
+            raise ValueError(f"render_sequence_denoised: 0 <= reach <= {_lib.TRAY_DENOISE_MAX_NEIGHBOURS // 2}")
+        if not frames:
+            return
+        spp = self._select_sampler(scene.device_scene(frames[0], self.device), config.spp)
+        if spp < 2:
+            raise ValueError("render_sequence_denoised: two half films need spp >= 2")
+        film = scene.flatten(frames[0]).contents.film
+        w, h = int(film.width), int(film.height)
+        held, spare = {}, []   # frame -> its (even, odd) on the device; pairs of frames that are done, to be rendered into again
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for f in frames:
+                window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
+                for g in window:
+                    if g not in held:
+                        pair = spare.pop() if spare else tuple(torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}") for _ in range(2))
+                        for half, rng in zip(pair, ((0, spp // 2), (spp // 2, spp))):
+                            half.zero_()
+                            self.render_samples_device(scene, g, config.select_blocks, spp, rng, half.data_ptr(), stream or None)
+                        held[g] = pair
+                out = self._denoise_temporal_device(held[f], [held[g] for g in window if g != f], radius, radius_t, patch, k)
+                for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
+                    spare.append(held.pop(g))
+                yield f, out.cpu().numpy()
+
     def render_shard_device(self, scene, frame, shard, n_shards, spp, rgbw_ptr, chunk_tiles=16, stream=None):
         """One rank's share of a frame (round-robin chunks of the Morton queue); merge = sum over ranks."""
         dev = scene.device_scene(frame, self.device)

@@ -14,6 +14,7 @@ MAT_MATTE, MAT_PLASTIC, MAT_METAL, MAT_GLASS, MAT_ROUGH_GLASS, MAT_SPECULAR_META
 FILTER_TABLE_SIZE = 16
 TRAY_PARTITION_TILES, TRAY_PARTITION_SAMPLES = 0, 1
 TRAY_DENOISE_RADIUS, TRAY_DENOISE_PATCH, TRAY_DENOISE_K = 7, 3, 0.45   # tray_denoise_device's defaults
+TRAY_DENOISE_RADIUS_T, TRAY_DENOISE_MAX_NEIGHBOURS = 3, 8   # tray_denoise_temporal_device's
 
 
 class TrayError(RuntimeError):
@@ -184,6 +185,9 @@ SYMBOLS = {
                                                   C.c_void_p, _P(C.c_uint32), _P(C.c_float), C.c_void_p]),
     "tray_denoise_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "tray_denoise_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p), _P(C.c_void_p), C.c_uint32,
+                                               C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tray_denoise_halves_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tray_noise_target_filtered_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),

@@ -11,6 +11,7 @@
 #include "noise.h"
 #include "denoise.h"
 #include "guide.h"
+#include "temporal.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 
@@ -1331,6 +1332,43 @@ int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, 
     }
     HIP_CHECK(hipSetDevice(g_device));
     tr_denoise::denoise(static_cast<hipStream_t>(stream_), even_dev, odd_dev, width, height, radius, patch, k, out_dev, scratch_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_scratch_bytes(uint32_t width, uint32_t height) { return tr_temporal::scratch_bytes(width, height); }
+
+int tray_denoise_temporal_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                 const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
+                                 float* out_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_temporal_device");
+    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    if (radius_t < 1u || radius_t > radius) { set_error(who + ": 1 <= radius_t <= radius is required"); return TRAY_E_INVALID; }
+    if (n_neighbours > TRAY_DENOISE_MAX_NEIGHBOURS) {
+        set_error(who + ": at most " + std::to_string(TRAY_DENOISE_MAX_NEIGHBOURS) + " neighbouring frames"); return TRAY_E_INVALID;
+    }
+    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const void* bufs[2u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 2u] = {even_dev, odd_dev, out_dev, scratch_dev};
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        if (!nb_even_dev[j] || !nb_odd_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
+        bufs[4u + 2u * j] = nb_even_dev[j];
+        bufs[5u + 2u * j] = nb_odd_dev[j];
+    }
+    if (!distinct_aligned(bufs, 4u + 2u * n_neighbours)) {
+        set_error(who + ": every frame's two films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_temporal::Layout l = tr_temporal::layout(scratch_dev, width, height);
+    // the centre's window first, then every neighbour's in the caller's order: each frame is prepare's two launches and one pass
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.centre);
+    tr_temporal::pass(stream, l.centre, l.centre, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, out_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
+        tr_temporal::pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
+    }
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;
 }

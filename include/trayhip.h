@@ -457,6 +457,50 @@ int tray_denoise_temporal_device(uint32_t width, uint32_t height, const float* e
 int tray_denoise_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                                const uint32_t* blocks_dev, uint32_t n_blocks, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream);
 
+/* tray_denoise_device with the weights measured on another pair of films: the patch distances come from the guide (GA, GB) = (guide_a_dev,
+ * guide_b_dev), the averaged colours from the values (even_dev, odd_dev). A guide with less noise than the values (a first pass's output)
+ * picks better weights than the values themselves can.
+ * - Values. a, b and valid are resolved from (even_dev, odd_dev) as tray_denoise_device resolves them.
+ * - Guide. ga = GA.rgb / GA.w, gb = GB.rgb / GB.w and gvalid by the same rule applied to (GA, GB): both weights > 0 and all eight words finite;
+ *   else ga = gb = 0. Vg = the 3 x 3 mean of (ga - gb)^2 / 2 over the gvalid pixels of the box (0 if there is none). The films of
+ *   tray_denoise_halves_device (weight 1 or 0) are valid guides as they stand.
+ * - Distance of p and q = p + o in guide buffer x (ga or gb): t(p', q') as in tray_denoise_device from x(p'), x(q'), Vg(p'), Vg(q');
+ *   pair(n) = gvalid(p') gvalid(q') (0 outside the image); d2_x(p, q) = sum_n t(p', q') pair(n) / (3 sum_n pair(n)) over the (2 patch + 1)^2
+ *   offsets n, p' = p + n, q' = q + n.
+ * - Weight. w_x(p, q) = exp(-max(0, d2_x)) if q is inside the image, valid(q) holds (the VALUES' validity) and sum_n pair(n) > 0, else 0.
+ * - Output. A(p) = sum_q w_gb(p, q) a(q) / sum_q w_gb(p, q), B(p) = sum_q w_ga(p, q) b(q) / sum_q w_ga(p, q); a quotient whose denominator is 0
+ *   is 0. out(p) = ((A + B) / 2, 1). A pixel that is invalid in the values and valid in the guide takes part in patches and is filled from its
+ *   window.
+ * - Order. dy outer, dx inner, ascending; f32, unfused, IEEE division, the library's own expf. No atomics: the same bits in every run. With
+ *   guide_a_dev == even_dev and guide_b_dev == odd_dev the output is tray_denoise_device's, bit for bit; the guide may alias the films for that.
+ * - Every output channel lies between the minimum and the maximum of that channel of a and b over the valid pixels of the pixel's window, up
+ *   to rounding: the guide only chooses weights.
+ * tray_denoise_guided_scratch_bytes: 96 bytes per pixel (the values' records and the guide's, 48 each; 0 if width or height is 0).
+ * tray_denoise_guided_device: five kernel launches on `stream` (tray_denoise_device's two preparing ones for the values, the same two for the
+ * guide, one filter over the 32 x 16 tiles), asynchronous, no host synchronisation, on the current device (tray_init).
+ * Returns TRAY_E_INVALID, before any device call, under tray_denoise_device's rules for width, height, radius, patch and k, if a pointer is
+ * null, if even_dev == odd_dev or guide_a_dev == guide_b_dev, unless out_dev and scratch_dev differ from all four films and from each other,
+ * or unless all six buffers are 16-byte aligned. */
+uint64_t tray_denoise_guided_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* guide_a_dev,
+                               const float* guide_b_dev, uint32_t radius, uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream);
+
+/* Two-pass NL-means: the second pass measures its patch distances on the first pass's output and averages the original films. By definition
+ * tray_denoise_halves_device(even_dev, odd_dev, radius, patch, k, blocks_dev = null) into (fa, fb), followed by
+ * tray_denoise_guided_device(even_dev, odd_dev, fa, fb, radius2, patch2, k2): the output is what those two calls give, bit for bit.
+ * tray_denoise_two_pass_scratch_bytes: 128 bytes per pixel (0 if width or height is 0), laid out as: the films' records, 48 bytes per pixel (the
+ * first pass's scratch, read again as the second pass's values); fa and fb, 16 each; the records of (fa, fb), 48.
+ * Six kernel launches on `stream`, in this order: the two preparing ones for the films, the first pass's filter (the halves) over the 32 x 16
+ * tiles, the two preparing ones for (fa, fb), the guided filter; asynchronous, no host synchronisation, on the current device (tray_init).
+ * Returns TRAY_E_INVALID, before any device call, under tray_denoise_device's rules for width, height and each of (radius, patch, k) and
+ * (radius2, patch2, k2), if a pointer is null, or unless the two films, out_dev and scratch_dev are four different buffers, 16-byte aligned. */
+#define TRAY_DENOISE_RADIUS2 5
+#define TRAY_DENOISE_PATCH2 1
+#define TRAY_DENOISE_K2 1.0f
+uint64_t tray_denoise_two_pass_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                                 uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream);
+
 /* tray_render_noise_target_device with the stopping rule on the image that will be shown: the rounds, the even / odd split, n_t, the outputs,
  * TrayKernelTiming and the error returns are that call's, word for word, and the films it returns are still the unfiltered films of exactly
  * [0, n_t) of every tile. One thing differs: the error of a tile in a round is that call's metric evaluated on (fa, fb) =

@@ -336,19 +336,32 @@ class Hip:
             print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
         return samples, err
 
-    def _denoise_device(self, even, odd, radius, patch, k):
-        """tray_denoise_device of two (h, w, 4) float32 tensors of this device on the current stream; returns the output tensor"""
+    def _denoise_device(self, even, odd, radius, patch, k, second=None):
+        """tray_denoise_device of two (h, w, 4) float32 tensors of this device on the current stream, or, with second = (radius2, patch2, k2),
+        tray_denoise_two_pass_device; returns the output tensor"""
         import torch
         h, w = int(even.shape[0]), int(even.shape[1])
+        nbytes = lib().tray_denoise_scratch_bytes if second is None else lib().tray_denoise_two_pass_scratch_bytes
         with torch.cuda.device(self.device):
             out = torch.empty_like(even)
-            scratch = torch.empty(max(int(lib().tray_denoise_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=even.device)
+            scratch = torch.empty(max(int(nbytes(w, h)), 16), dtype=torch.uint8, device=even.device)
             stream = torch.cuda.current_stream().cuda_stream
             check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_device(w, h, C.c_void_p(even.data_ptr()), C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k),
-                                            C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            head = (w, h, C.c_void_p(even.data_ptr()), C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k))
+            tail = (C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None)
+            if second is None:
+                check(lib().tray_denoise_device(*head, *tail))
+            else:
+                check(lib().tray_denoise_two_pass_device(*head, int(second[0]), int(second[1]), float(second[2]), *tail))
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out
+
+    @staticmethod
+    def _second_pass(what, passes, radius2, patch2, k2):
+        """None for one pass, (radius2, patch2, k2) for two"""
+        if passes not in (1, 2):
+            raise ValueError(f"{what}: passes must be 1 or 2, not {passes!r}")
+        return None if passes == 1 else (radius2, patch2, k2)
 
     def _films_on_device(self, what, even, odd):
         """(as_numpy, e, o): two (h, w, 4) films -- numpy arrays or torch tensors on this device -- as two contiguous float32 tensors"""
@@ -369,12 +382,39 @@ class Hip:
             raise ValueError(f"{what}: even and odd must be two (h, w, 4) films of one size")
         return as_numpy, e, o
 
-    def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+    def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, passes=1,
+                radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2):
         """The dual-buffer NL-means filter of include/trayhip.h (tray_denoise_device) of two half films, e.g. the even and odd film of a
         noise-target render: two (h, w, 4) float32 RGBW arrays -- numpy arrays or torch tensors on this device -- in, the same kind out: an RGBW
-        film of weight 1. Pixels of weight <= 0 or with a non-finite component count as missing and are filled from their neighbourhood."""
+        film of weight 1. Pixels of weight <= 0 or with a non-finite component count as missing and are filled from their neighbourhood.
+        passes=2 (tray_denoise_two_pass_device): a second pass of (radius2, patch2, k2) takes its weights from the first pass's output and
+        averages the films again."""
+        second = self._second_pass("denoise", passes, radius2, patch2, k2)
         as_numpy, e, o = self._films_on_device("denoise", even, odd)
-        out = self._denoise_device(e, o, radius, patch, k)
+        out = self._denoise_device(e, o, radius, patch, k, second)
+        return out.cpu().numpy() if as_numpy else out
+
+    def denoise_guided(self, even, odd, guide_a, guide_b, radius=_lib.TRAY_DENOISE_RADIUS2, patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
+        """denoise() with the weights measured on another pair of films (tray_denoise_guided_device): the patch distances come from (guide_a,
+        guide_b), e.g. denoise_halves() of the same films, the averaged colours from (even, odd). Films in and out as for denoise(), all four of
+        one kind and one size. With the films as their own guide the image is denoise()'s to the bit."""
+        import torch
+        as_numpy, e, o = self._films_on_device("denoise_guided", even, odd)
+        guide_numpy, ga, gb = self._films_on_device("denoise_guided", guide_a, guide_b)
+        if guide_numpy != as_numpy:
+            raise TypeError("denoise_guided: the films and the guide must all be numpy arrays or all be torch tensors")
+        if ga.shape != e.shape:
+            raise ValueError("denoise_guided: the guide must have the films' size")
+        h, w = int(e.shape[0]), int(e.shape[1])
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_guided_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_guided_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(ga.data_ptr()),
+                                                   C.c_void_p(gb.data_ptr()), int(radius), int(patch), float(k), C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out.cpu().numpy() if as_numpy else out
 
     def denoise_halves(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
@@ -396,15 +436,20 @@ class Hip:
         return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
 
     def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
-                        k=_lib.TRAY_DENOISE_K, error="raw"):
+                        k=_lib.TRAY_DENOISE_K, error="raw", passes=1, radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2,
+                        k2=_lib.TRAY_DENOISE_K2):
         """config.select_blocks of the frame rendered as two half films and denoised on the device (tray_denoise_device); the RGBW output (weight 1)
         is added into rt. With `threshold` the films are the even / odd film of a noise-target render (see render_noise_target; error="filtered"
         stops on the error of the denoised image and takes the output from that same call) and (tile_samples, tile_error) is returned; without it
         they are the sample ranges [0, spp / 2) and [spp / 2, spp) of the round_spp(config.spp)-sample frame (spp >= 2) and None is returned.
-        LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        passes=2 filters the films as denoise(passes=2) does; the stopping rule of error="filtered" measures one pass's image, so the two do not
+        combine. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
         import torch
         if error not in ("raw", "filtered"):
             raise ValueError(f"error must be 'raw' or 'filtered', not {error!r}")
+        second = self._second_pass("render_denoised", passes, radius2, patch2, k2)
+        if second is not None and error == "filtered":
+            raise ValueError("render_denoised: error='filtered' stops on one pass's image and takes it from that call; use passes=1 with it")
         if error == "filtered" and threshold is None:
             raise ValueError("render_denoised: error='filtered' is a stopping rule and needs a threshold")
         dev = scene.device_scene(config.current_frame, self.device)
@@ -429,7 +474,7 @@ class Hip:
             if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:   # (the last render call's: the whole noise-target call, or the second range)
                 self.last_timing = t
             if out is None:
-                out = self._denoise_device(even, odd, radius, patch, k)
+                out = self._denoise_device(even, odd, radius, patch, k, second)
             rt.add_pixels(out.reshape(-1).cpu().numpy())
         return result
 

@@ -12,6 +12,7 @@
 #include "denoise.h"
 #include "guide.h"
 #include "temporal.h"
+#include "guided.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 
@@ -1369,6 +1370,60 @@ int tray_denoise_temporal_device(uint32_t width, uint32_t height, const float* e
         tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
         tr_temporal::pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
     }
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_guided_scratch_bytes(uint32_t width, uint32_t height) { return tr_guided::scratch_bytes(width, height); }
+
+int tray_denoise_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* guide_a_dev, const float* guide_b_dev,
+                               uint32_t radius, uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_guided_device");
+    if (!even_dev || !odd_dev || !guide_a_dev || !guide_b_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    // (the guide may be the films themselves: then the call is tray_denoise_device)
+    const void* const inputs[4] = {even_dev, odd_dev, guide_a_dev, guide_b_dev};
+    bool ok = even_dev != odd_dev && guide_a_dev != guide_b_dev && out_dev != scratch_dev &&
+              ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(scratch_dev)) & 15u) == 0u;
+    for (const void* in : inputs) ok = ok && (reinterpret_cast<uintptr_t>(in) & 15u) == 0u && in != out_dev && in != scratch_dev;
+    if (!ok) {
+        set_error(who + ": the two films must differ, the two guide films must differ, the output and the scratch buffer must differ from all four "
+                        "and from each other, and all six must be 16-byte aligned");
+        return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_guided::Layout l = tr_guided::layout(scratch_dev, width, height);
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
+    tr_denoise::prepare(stream, guide_a_dev, guide_b_dev, width, height, l.guide);
+    tr_guided::filter(stream, l.guide, l.values, width, height, radius, patch, k, out_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return tr_guided::two_pass_scratch_bytes(width, height); }
+
+int tray_denoise_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                                 uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_two_pass_device");
+    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    rc = denoise_args((who + ", second pass").c_str(), width, height, radius2, patch2, k2);
+    if (rc != TRAY_OK) return rc;
+    const void* const bufs[4] = {even_dev, odd_dev, out_dev, scratch_dev};
+    if (!distinct_aligned(bufs, 4u)) {
+        set_error(who + ": the two films, the output and the scratch buffer must be four different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_guided::TwoPassLayout l = tr_guided::two_pass_layout(scratch_dev, width, height);
+    // the first pass, as tray_denoise_halves_device over every block; its records of the films are the second pass's values
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
+    tr_guide::halves(stream, l.values, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
+    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
+    tr_guided::filter(stream, l.guide, l.values, width, height, radius2, patch2, k2, out_dev);
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;
 }

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(DN_BLOCK) void k_dn_filter_halves(const float4* __r
                                                                float4* __restrict__ fb) {
     const uint32_t block = blocks ? blocks[blockIdx.x] : blockIdx.x;
     if (block >= dn_tiles_x(width) * dn_tiles_y(height)) return;   // (the same for every thread of the workgroup)
-    const dn_halves h = dn_filter_block<F>(scratch, width, height, radius, k, block);
+    const dn_halves h = dn_normalise(dn_filter_block<F>(scratch, nullptr, nullptr, width, height, radius, k, block, nullptr));
     if (h.px < width && h.py < height) {
         fa[(size_t)h.py * width + h.px] = h.A;
         fb[(size_t)h.py * width + h.px] = h.B;

@@ -351,6 +351,27 @@ int tray_render_shard_device(TrayDeviceScene* s, uint32_t shard, uint32_t n_shar
 int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp,
                                uint32_t sample_begin, uint32_t sample_end, uint64_t seed, float* rgbw_dev, void* stream);
 
+/* First-hit feature films: where the camera rays of the samples [sample_begin, sample_end) of tray_render_samples_device's frame first land,
+ * added into three RGBW films of their own (get_renderf32 layout, zeroed by the caller): albedo, shading normal, depth.
+ * - Sample. Camera sample (px, py, s) of the spp-sample LowDiscrepancy frame under `seed` is (sx, sy, time), the result of pixel_sample; its
+ *   ray is camera_ray(sx, sy, time), its hit Scene::intersect's (scene.rs:148-150): the position, ray and first hit that
+ *   tray_render_samples_device traces for that sample.
+ * - hit is 1 or 0.
+ * - albedo: (0, 0, 0) on a miss. MATTE and PLASTIC: the material's c0 -- the constant, or Texture::sample_color of tex_c0 at the hit's
+ *   (u, v, ray.time). Every other material kind, and an instance with material_id == 0xffffffff: (1, 1, 1). No clamping; an emitter's
+ *   material counts like any other.
+ * - normal: TrayHit.n as tray_debug_intersect reports it -- world space, not flipped towards the ray --, 0 on a miss.
+ * - depth: (TrayHit.t, hit, 0), with t = 0 on a miss: the resolved film's r / g is the mean distance over the samples that hit, g the coverage.
+ * - Films. Each of the three colours goes through RenderTarget::write at (sx, sy) (render_target.rs:77-165), as a radiance sample does, so the
+ *   three w planes are the colour film's of the same samples up to the order of the f32 sums, and the films line up with the colour films
+ *   weight for weight. Ranges that partition [0, spp) add up; both halves may go into one film.
+ * tile_count == 0 selects the whole queue. One kernel launch on `stream`, asynchronous, no host synchronisation, whatever schedule renders the
+ * scene; TrayKernelTiming is not touched. Returns TRAY_E_INVALID under tray_render_samples_device's rules, if a film is null, if two of the
+ * three films are the same buffer or if a film is not 16-byte aligned; TRAY_E_UNSUPPORTED under Uniform / Adaptive, as that call. Normal and
+ * depth have no consumer inside the library: they are films for the caller (external denoisers, compositing). */
+int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint32_t sample_begin,
+                                 uint32_t sample_end, uint64_t seed, float* albedo_dev, float* normal_dev, float* depth_dev, void* stream);
+
 /* Render to a noise threshold: tiles [tile_start, tile_start+tile_count) of the max_spp-sample LowDiscrepancy frame, each tile sampled until
  * its estimated error drops below `threshold` (tile_count == 0 selects the whole queue, as in tray_render_tiles_device).
  * - Rounds. Round 0 renders the samples [0, min_spp) of every tile; round r >= 1 renders [min_spp 2^(r-1), min_spp 2^r) of the tiles that are
@@ -500,6 +521,24 @@ int tray_denoise_guided_device(uint32_t width, uint32_t height, const float* eve
 uint64_t tray_denoise_two_pass_scratch_bytes(uint32_t width, uint32_t height);
 int tray_denoise_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                                  uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream);
+
+/* Albedo-demodulated denoising: the colour is divided by the first-hit albedo (tray_render_first_hit_device's film of the same frame), the
+ * smooth remainder is filtered, and the texture is multiplied back in.
+ * - With ALB the pixel of albedo_dev: s_c(p) = max(ALB_c / ALB.w, 0) + TRAY_DEMOD_EPS where ALB.w > 0 and all four words are finite, else
+ *   s_c(p) = 1 (the resolved albedo goes slightly negative at texture edges under a filter with negative lobes: hence the max).
+ * - E'(p) = (E.rgb / s, E.w), O' likewise. D = tray_denoise_device(E', O', radius, patch, k), or tray_denoise_two_pass_device(E', O', radius,
+ *   patch, k, radius2, patch2, k2) when radius2 >= 1; radius2 == 0 means one pass. out = (D.rgb * s, 1). f32, unfused, IEEE division.
+ * - An albedo film without a valid pixel gives the plain call's bits.
+ * tray_denoise_demodulated_scratch_bytes: the filter's scratch (48 or 128 bytes per pixel) plus 32 for E' and O' behind it; 0 if width or
+ * height is 0. Launches in stream order, no host synchronisation, on the current device: one that writes E' and O', the filter's three (or
+ * six), one that scales out_dev in place: 5 or 8.
+ * Returns TRAY_E_INVALID, before any device call, under tray_denoise_device's (and the two-pass call's) rules for the filter parameters and
+ * the buffers, or if albedo_dev is null, equals another buffer or is not 16-byte aligned. */
+#define TRAY_DEMOD_EPS 0.01f
+uint64_t tray_denoise_demodulated_scratch_bytes(uint32_t width, uint32_t height, uint32_t radius2);
+int tray_denoise_demodulated_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                    uint32_t radius, uint32_t patch, float k, uint32_t radius2, uint32_t patch2, float k2, float* out_dev,
+                                    void* scratch_dev, void* stream);
 
 /* tray_render_noise_target_device with the stopping rule on the image that will be shown: the rounds, the even / odd split, n_t, the outputs,
  * TrayKernelTiming and the error returns are that call's, word for word, and the films it returns are still the unfiltered films of exactly
@@ -670,6 +709,11 @@ int tray_debug_intersect(TrayDeviceScene* s, uint32_t n, const TrayRay* rays, Tr
  * [5] = number of path vertices, [6] = number of rays, [7] = 0. */
 int tray_debug_sample_radiance(TrayDeviceScene* s, uint32_t n, const uint32_t* px, const uint32_t* py,
                                const uint32_t* si, uint32_t spp, uint64_t seed, float* out);
+
+/* The first hit of individual camera samples (tray_render_first_hit_device's per-sample statement), items as above:
+ * out[i*12 + 0..2] = sample x, y, time, [3..5] = albedo rgb, [6..8] = normal xyz, [9] = t, [10] = hit, [11] = 0. */
+int tray_debug_first_hit(TrayDeviceScene* s, uint32_t n, const uint32_t* px, const uint32_t* py, const uint32_t* si, uint32_t spp,
+                         uint64_t seed, float* out);
 
 /* BSDF::eval / pdf / sample (src/bxdf/bsdf.rs:66-125) of material `material_id` on a canonical
  * frame (n = +z, dp_du = +x). For item i: wo = dirs[i*6..+3], wi = dirs[i*6+3..+6], u = u3[i*3..+3]

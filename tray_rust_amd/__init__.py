@@ -261,6 +261,33 @@ class Hip:
                                                C.c_void_p(int(rgbw_ptr)), C.c_void_p(int(stream)) if stream else None))
         return dev
 
+    def render_first_hit_device(self, scene, frame, select_blocks, spp, sample_range, albedo_ptr, normal_ptr, depth_ptr, stream=None):
+        """Asynchronous: the first-hit feature films of the samples [begin, end) = sample_range of every pixel of select_blocks of the spp-sample
+        LowDiscrepancy frame -- the camera rays render_samples_device traces for them --, accumulated into three device RGBW buffers: albedo,
+        shading normal, depth as (distance, coverage, 0) (tray_render_first_hit_device). Ranges add up, weight for weight with the colour film."""
+        dev = scene.device_scene(frame, self.device)
+        spp = self._select_sampler(dev, spp)
+        begin, end = (int(v) for v in sample_range)
+        check(lib().tray_render_first_hit_device(dev, int(select_blocks[0]), int(select_blocks[1]), int(spp), begin, end, self.seed,
+                                                 C.c_void_p(int(albedo_ptr)), C.c_void_p(int(normal_ptr)), C.c_void_p(int(depth_ptr)),
+                                                 C.c_void_p(int(stream)) if stream else None))
+        return dev
+
+    def render_first_hit(self, scene, config, sample_range=None):
+        """The first-hit films of config.select_blocks of the frame as a dict of three (h, w, 4) numpy RGBW films, "albedo", "normal" and "depth"
+        (render_first_hit_device), of the samples sample_range (default: all) of the round_spp(config.spp)-sample frame."""
+        import torch
+        flat = scene.flatten(config.current_frame).contents.film
+        w, h = int(flat.width), int(flat.height)
+        spp = round_spp(config.spp)
+        with torch.cuda.device(self.device):
+            films = [torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}") for _ in range(3)]
+            stream = torch.cuda.current_stream().cuda_stream
+            self.render_first_hit_device(scene, config.current_frame, config.select_blocks, spp, sample_range or (0, spp),
+                                         *[f.data_ptr() for f in films], stream or None)
+            torch.cuda.current_stream().synchronize()
+            return {name: f.cpu().numpy() for name, f in zip(("albedo", "normal", "depth"), films)}
+
     def render_progressive(self, scene, rt, config, passes):
         """Generator: config.select_blocks of the frame in `passes` consecutive sample ranges of nearly equal size ([k spp / passes,
         (k + 1) spp / passes), at most spp of them), each added into rt as it is done; yields (samples_done, rt) after every pass. After the
@@ -336,12 +363,16 @@ class Hip:
             print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
         return samples, err
 
-    def _denoise_device(self, even, odd, radius, patch, k, second=None):
+    def _denoise_device(self, even, odd, radius, patch, k, second=None, albedo=None):
         """tray_denoise_device of two (h, w, 4) float32 tensors of this device on the current stream, or, with second = (radius2, patch2, k2),
-        tray_denoise_two_pass_device; returns the output tensor"""
+        tray_denoise_two_pass_device; with an albedo film (a third such tensor) tray_denoise_demodulated_device of either; returns the output
+        tensor"""
         import torch
         h, w = int(even.shape[0]), int(even.shape[1])
-        nbytes = lib().tray_denoise_scratch_bytes if second is None else lib().tray_denoise_two_pass_scratch_bytes
+        if albedo is not None:
+            nbytes = lambda w_, h_: lib().tray_denoise_demodulated_scratch_bytes(w_, h_, 0 if second is None else int(second[0]))
+        else:
+            nbytes = lib().tray_denoise_scratch_bytes if second is None else lib().tray_denoise_two_pass_scratch_bytes
         with torch.cuda.device(self.device):
             out = torch.empty_like(even)
             scratch = torch.empty(max(int(nbytes(w, h)), 16), dtype=torch.uint8, device=even.device)
@@ -349,7 +380,10 @@ class Hip:
             check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
             head = (w, h, C.c_void_p(even.data_ptr()), C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k))
             tail = (C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None)
-            if second is None:
+            if albedo is not None:
+                r2, f2, k2 = (0, 0, 1.0) if second is None else second   # (radius2 == 0: one pass)
+                check(lib().tray_denoise_demodulated_device(*head[:4], C.c_void_p(albedo.data_ptr()), *head[4:], int(r2), int(f2), float(k2), *tail))
+            elif second is None:
                 check(lib().tray_denoise_device(*head, *tail))
             else:
                 check(lib().tray_denoise_two_pass_device(*head, int(second[0]), int(second[1]), float(second[2]), *tail))
@@ -383,15 +417,23 @@ class Hip:
         return as_numpy, e, o
 
     def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, passes=1,
-                radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2):
+                radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2, albedo=None):
         """The dual-buffer NL-means filter of include/trayhip.h (tray_denoise_device) of two half films, e.g. the even and odd film of a
         noise-target render: two (h, w, 4) float32 RGBW arrays -- numpy arrays or torch tensors on this device -- in, the same kind out: an RGBW
         film of weight 1. Pixels of weight <= 0 or with a non-finite component count as missing and are filled from their neighbourhood.
         passes=2 (tray_denoise_two_pass_device): a second pass of (radius2, patch2, k2) takes its weights from the first pass's output and
-        averages the films again."""
+        averages the films again. albedo: a first-hit albedo film of the same frame (render_first_hit), of the films' kind and size: the
+        colour is divided by it, the remainder filtered and the texture multiplied back in (tray_denoise_demodulated_device)."""
         second = self._second_pass("denoise", passes, radius2, patch2, k2)
         as_numpy, e, o = self._films_on_device("denoise", even, odd)
-        out = self._denoise_device(e, o, radius, patch, k, second)
+        alb = None
+        if albedo is not None:
+            albedo_numpy, alb, _ = self._films_on_device("denoise", albedo, albedo)
+            if albedo_numpy != as_numpy:
+                raise TypeError("denoise: the films and the albedo film must all be numpy arrays or all be torch tensors")
+            if alb.shape != e.shape:
+                raise ValueError("denoise: the albedo film must have the films' size")
+        out = self._denoise_device(e, o, radius, patch, k, second, *(() if alb is None else (alb,)))
         return out.cpu().numpy() if as_numpy else out
 
     def denoise_guided(self, even, odd, guide_a, guide_b, radius=_lib.TRAY_DENOISE_RADIUS2, patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
@@ -437,23 +479,30 @@ class Hip:
 
     def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
                         k=_lib.TRAY_DENOISE_K, error="raw", passes=1, radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2,
-                        k2=_lib.TRAY_DENOISE_K2):
+                        k2=_lib.TRAY_DENOISE_K2, demodulate=False, feature_spp=None):
         """config.select_blocks of the frame rendered as two half films and denoised on the device (tray_denoise_device); the RGBW output (weight 1)
         is added into rt. With `threshold` the films are the even / odd film of a noise-target render (see render_noise_target; error="filtered"
         stops on the error of the denoised image and takes the output from that same call) and (tile_samples, tile_error) is returned; without it
         they are the sample ranges [0, spp / 2) and [spp / 2, spp) of the round_spp(config.spp)-sample frame (spp >= 2) and None is returned.
         passes=2 filters the films as denoise(passes=2) does; the stopping rule of error="filtered" measures one pass's image, so the two do not
-        combine. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        combine. demodulate=True divides the colour by the frame's first-hit albedo before the filter and multiplies it back in afterwards
+        (denoise(albedo=...)): the albedo film is rendered from the samples [0, feature_spp or spp) of the same frame and seed; it does not
+        combine with error="filtered" either. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
         import torch
         if error not in ("raw", "filtered"):
             raise ValueError(f"error must be 'raw' or 'filtered', not {error!r}")
         second = self._second_pass("render_denoised", passes, radius2, patch2, k2)
         if second is not None and error == "filtered":
             raise ValueError("render_denoised: error='filtered' stops on one pass's image and takes it from that call; use passes=1 with it")
+        if demodulate and error == "filtered":
+            raise ValueError("render_denoised: error='filtered' stops on the undemodulated image and takes it from that call; use demodulate=False with it")
         if error == "filtered" and threshold is None:
             raise ValueError("render_denoised: error='filtered' is a stopping rule and needs a threshold")
         dev = scene.device_scene(config.current_frame, self.device)
         spp = self._select_sampler(dev, config.spp)
+        n_feat = spp if feature_spp is None else int(feature_spp)
+        if demodulate and not 1 <= n_feat <= spp:
+            raise ValueError(f"render_denoised: feature_spp must lie in [1, {spp}]")
         start, count = (int(v) for v in config.select_blocks)
         w, h = rt.dimensions()
         result, out = None, None
@@ -474,7 +523,12 @@ class Hip:
             if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:   # (the last render call's: the whole noise-target call, or the second range)
                 self.last_timing = t
             if out is None:
-                out = self._denoise_device(even, odd, radius, patch, k, second)
+                albedo = None
+                if demodulate:
+                    albedo, normal, depth = (torch.zeros_like(even) for _ in range(3))
+                    self.render_first_hit_device(scene, config.current_frame, (start, count), spp, (0, n_feat), albedo.data_ptr(), normal.data_ptr(),
+                                                 depth.data_ptr(), stream or None)
+                out = self._denoise_device(even, odd, radius, patch, k, second, *(() if albedo is None else (albedo,)))
             rt.add_pixels(out.reshape(-1).cpu().numpy())
         return result
 

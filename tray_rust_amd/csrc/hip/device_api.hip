@@ -13,6 +13,7 @@
 #include "guide.h"
 #include "temporal.h"
 #include "guided.h"
+#include "first_hit.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 
@@ -1096,6 +1097,30 @@ int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t
     return launch_tiles(s, s->d_tiles + tile_start, w.work, w.chunk, w.chunk_stride, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
 }
 
+static bool distinct_aligned(const void* const* bufs, size_t n);
+// the ANIM argument of the first-hit kernels: the set the debug kernels have (2: the spline stacks evaluated at every use, no transform cache)
+static int first_hit_anim(const TrayDeviceScene* s) { return s->deforming ? 3 : s->animated ? 2 : 0; }
+
+int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint32_t sample_begin, uint32_t sample_end,
+                                 uint64_t seed, float* albedo_dev, float* normal_dev, float* depth_dev, void* stream_) {
+    const std::string who("tray_render_first_hit_device");
+    if (!s || !albedo_dev || !normal_dev || !depth_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID; }
+    if (sample_begin >= sample_end || sample_end > spp) { set_error(who + ": the range must satisfy sample_begin < sample_end <= spp"); return TRAY_E_INVALID; }
+    const void* const films[3] = {albedo_dev, normal_dev, depth_dev};
+    if (!distinct_aligned(films, 3u)) { set_error(who + ": the three films must be different buffers, 16-byte aligned"); return TRAY_E_INVALID; }
+    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error(who + ": sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
+    if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
+    tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
+    HIP_CHECK(hipSetDevice(s->device));
+    if (tile_count == 0) return TRAY_OK;   // (an empty queue: nothing to add)
+    // s->dev, not the launch copy: no per-path transform cache and no table, so the call needs none of a render's launch buffers
+    tr_firsthit::tiles(first_hit_anim(s), static_cast<hipStream_t>(stream_), s->stack_bytes, s->dev, s->d_tiles + tile_start, tile_count, spp,
+                       tr_rules::frame_key(seed, s->dev.frame), sample_begin, sample_end, albedo_dev, normal_dev, depth_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
 // What the filtered stopping rule adds to a round (tray_render_noise_target_filtered_device): the filter's arguments and the private scratch layout
 // [filter records: 48 bytes per pixel | fa | fb: RGBW films | flags | list: one word per 32 x 16 block | counts: tiles, blocks, 2 words of padding]
 struct GuideRounds {
@@ -1404,6 +1429,17 @@ int tray_denoise_guided_device(uint32_t width, uint32_t height, const float* eve
 
 uint64_t tray_denoise_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return tr_guided::two_pass_scratch_bytes(width, height); }
 
+// the six launches of a two-pass call: the first pass as tray_denoise_halves_device over every block -- its records of the films are the second
+// pass's values --, then the guided filter with the pilot as guide
+static void two_pass_launches(hipStream_t stream, uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch,
+                              float k, uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev) {
+    const tr_guided::TwoPassLayout l = tr_guided::two_pass_layout(scratch_dev, width, height);
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
+    tr_guide::halves(stream, l.values, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
+    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
+    tr_guided::filter(stream, l.guide, l.values, width, height, radius2, patch2, k2, out_dev);
+}
+
 int tray_denoise_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                                  uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream_) {
     const std::string who("tray_denoise_two_pass_device");
@@ -1417,13 +1453,41 @@ int tray_denoise_two_pass_device(uint32_t width, uint32_t height, const float* e
         set_error(who + ": the two films, the output and the scratch buffer must be four different buffers, 16-byte aligned"); return TRAY_E_INVALID;
     }
     HIP_CHECK(hipSetDevice(g_device));
+    two_pass_launches(static_cast<hipStream_t>(stream_), width, height, even_dev, odd_dev, radius, patch, k, radius2, patch2, k2, out_dev, scratch_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_demodulated_scratch_bytes(uint32_t width, uint32_t height, uint32_t radius2) {
+    if (width == 0u || height == 0u) return 0u;
+    return (radius2 ? tr_guided::two_pass_scratch_bytes(width, height) : tr_denoise::scratch_bytes(width, height)) + tr_firsthit::demod_bytes(width, height);
+}
+
+int tray_denoise_demodulated_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev, uint32_t radius,
+                                    uint32_t patch, float k, uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_demodulated_device");
+    if (!even_dev || !odd_dev || !albedo_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    if (radius2 != 0u) {
+        rc = denoise_args((who + ", second pass").c_str(), width, height, radius2, patch2, k2);
+        if (rc != TRAY_OK) return rc;
+    }
+    const void* const bufs[5] = {even_dev, odd_dev, albedo_dev, out_dev, scratch_dev};
+    if (!distinct_aligned(bufs, 5u)) {
+        set_error(who + ": the two films, the albedo film, the output and the scratch buffer must be five different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_guided::TwoPassLayout l = tr_guided::two_pass_layout(scratch_dev, width, height);
-    // the first pass, as tray_denoise_halves_device over every block; its records of the films are the second pass's values
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
-    tr_guide::halves(stream, l.values, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
-    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
-    tr_guided::filter(stream, l.guide, l.values, width, height, radius2, patch2, k2, out_dev);
+    // [the filter's scratch | E' | O']
+    const size_t film = (size_t)width * height * 16u;
+    char* const after = static_cast<char*>(scratch_dev) + (radius2 ? tr_guided::two_pass_scratch_bytes(width, height) : tr_denoise::scratch_bytes(width, height));
+    float* const e = reinterpret_cast<float*>(after);
+    float* const o = reinterpret_cast<float*>(after + film);
+    tr_firsthit::demodulate(stream, even_dev, odd_dev, albedo_dev, width, height, e, o);
+    if (radius2) two_pass_launches(stream, width, height, e, o, radius, patch, k, radius2, patch2, k2, out_dev, scratch_dev);
+    else tr_denoise::denoise(stream, e, o, width, height, radius, patch, k, out_dev, scratch_dev);
+    tr_firsthit::remodulate(stream, albedo_dev, width, height, out_dev);
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;
 }
@@ -2096,6 +2160,31 @@ int tray_debug_sample_radiance(TrayDeviceScene* s, uint32_t n, const uint32_t* p
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     if (e != hipSuccess) { set_error(std::string("tray_debug_sample_radiance: ") + hipGetErrorString(e)); return TRAY_E_DEVICE; }
+    return TRAY_OK;
+}
+
+int tray_debug_first_hit(TrayDeviceScene* s, uint32_t n, const uint32_t* px, const uint32_t* py, const uint32_t* si, uint32_t spp, uint64_t seed, float* out) {
+    if (!s || !px || !py || !si || !out) { set_error("tray_debug_first_hit: null argument"); return TRAY_E_INVALID; }
+    if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two"); return TRAY_E_INVALID; }
+    if (n == 0) return TRAY_OK;
+    for (uint32_t i = 0; i < n; ++i)
+        if (px[i] >= s->dev.width || py[i] >= s->dev.height || si[i] >= spp) { set_error("tray_debug_first_hit: item out of range"); return TRAY_E_INVALID; }
+    HIP_CHECK(hipSetDevice(s->device));
+    uint32_t* d_in = nullptr;
+    float* d_out = nullptr;
+    HIP_CHECK(hipMalloc(&d_in, 3 * (size_t)n * sizeof(uint32_t)));
+    hipError_t e = hipMalloc(&d_out, 12 * (size_t)n * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_in, px, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_in + n, py, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_in + 2 * (size_t)n, si, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        tr_firsthit::debug(first_hit_anim(s), s->stack_bytes, s->dev, n, d_in, d_in + n, d_in + 2 * (size_t)n, spp, tr_rules::frame_key(seed, s->dev.frame), d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, 12 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) { set_error(std::string("tray_debug_first_hit: ") + hipGetErrorString(e)); return TRAY_E_DEVICE; }
     return TRAY_OK;
 }
 

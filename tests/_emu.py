@@ -83,8 +83,23 @@ def emu(defines=()):
         h.emu_wf_bin.argtypes = [C.c_uint32] + [C.c_void_p] * 6 + [C.c_int]
         h.emu_film_splat.restype = C.c_int
         h.emu_film_splat.argtypes = [C.POINTER(L.TrayFilm), C.c_int] + [C.c_uint32] * 5 + [C.c_void_p, C.c_void_p]
+        h.emu_scene_plan.restype = C.c_int
+        h.emu_scene_plan.argtypes = [FS, C.c_int, C.c_int, C.c_void_p]
         _libs[key] = h
     return _libs[key]
+
+
+# emu_kernels.cpp: emu_scene_plan -- the fields of tr_plan::ScenePlan, then the constants of the LDS layout
+PLAN_FIELDS = ("deforming", "animated", "anim_debug", "feat", "light_filter", "mat_kinds_present", "film_rows_ok", "wavefront", "mesh_depth", "depth",
+               "coop_offset", "win_offset", "stack_bytes", "n_moving", "xf_movable", "TR_BLOCK", "TR_COOP_MAX_TRIS", "TR_COOP_WORDS", "TR_FLAT_MAX", "WIN_PLANE")
+
+
+def scene_plan(flat, coop=-1, film_rows=-1):
+    """what the library decides about the scene (csrc/hip/scene_plan.h), without its environment overrides: {field: value}; coop / film_rows as for
+    render_tiles"""
+    out = np.zeros(len(PLAN_FIELDS), np.uint32)
+    assert emu().emu_scene_plan(flat, coop, film_rows, out.ctypes.data) == 0
+    return {k: int(v) for k, v in zip(PLAN_FIELDS, out)}
 
 
 def retraced(defines=()):

@@ -1,13 +1,9 @@
 // Host emulation of the first-hit kernels (tray_rust_amd/csrc/hip/first_hit_kernels.h): k_debug_first_hit one thread at a time, k_first_hit_tiles as
 // SIMT fibers (256 per workgroup: the wave-uniform sample loop, the LDS window, the barrier and the flush run as the device runs them), and the
 // two element-wise kernels of tray_denoise_demodulated_device. Built by tests/_first_hit_ref.py over emu_kernels.cpp, whose scene set-up it uses;
-// the launches follow device_api.hip's: the ANIM set of the debug kernels, the scene's own stacks with the cooperative leaf test's area behind them.
+// the launches follow device_api.hip's: the ANIM set of the debug kernels and the scene's own dynamic LDS, both from its plan (scene_plan.h).
 #include "emu_kernels.cpp"
 #include "../../tray_rust_amd/csrc/hip/first_hit_kernels.h"
-
-namespace {
-int first_hit_anim(const TrayFlatScene* f) { return deforming(f) ? 3 : scene_moves(f) ? 2 : 0; }
-}
 
 extern "C" {
 
@@ -18,7 +14,7 @@ int emu_debug_first_hit(const TrayFlatScene* f, uint32_t n, const uint32_t* px, 
     make_scene(f, e);
     const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
     const uint32_t grid = (n + TR_BLOCK - 1) / TR_BLOCK;
-    const int anim = first_hit_anim(f);
+    const int anim = e.plan.anim_debug();
     if (anim == 3) launch(grid, TR_BLOCK, [&] { k_debug_first_hit<3>(e.d, n, px, py, si, spp, kf, out); });
     else if (anim) launch(grid, TR_BLOCK, [&] { k_debug_first_hit<2>(e.d, n, px, py, si, spp, kf, out); });
     else launch(grid, TR_BLOCK, [&] { k_debug_first_hit<0>(e.d, n, px, py, si, spp, kf, out); });
@@ -32,15 +28,12 @@ int emu_render_first_hit(const TrayFlatScene* f, const uint32_t* tiles_xy, uint3
     if (tile_count == 0u) return 0;
     EmuScene e;
     make_scene(f, e);
-    uint32_t stack_words = e.depth * TR_BLOCK;
-    bool small_mesh = false;
-    for (uint32_t m = 0; m < f->n_meshes; ++m) small_mesh = small_mesh || f->meshes[m].tri_count <= TR_COOP_MAX_TRIS;
-    if (small_mesh && f->n_instances <= TR_FLAT_MAX) { e.d.coop_offset = stack_words; stack_words += (TR_BLOCK / 64) * TR_COOP_WORDS; }   // tray_scene_create
+    lds_layout(f, e, true, true);
     std::vector<uint2> tiles(tile_count);
     for (uint32_t i = 0; i < tile_count; ++i) tiles[i] = make_uint2(tiles_xy[2 * i], tiles_xy[2 * i + 1]);
     const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
-    const int anim = first_hit_anim(f);
-    const size_t lds = (size_t)stack_words * 4;
+    const int anim = e.plan.anim_debug();
+    const size_t lds = e.plan.stack_bytes;
     if (anim == 3) return launch_simt(tile_count, TR_BLOCK, [&] { k_first_hit_tiles<3>(e.d, tiles.data(), spp, kf, smp_begin, smp_end, albedo, normal, depth); }, lds);
     if (anim) return launch_simt(tile_count, TR_BLOCK, [&] { k_first_hit_tiles<2>(e.d, tiles.data(), spp, kf, smp_begin, smp_end, albedo, normal, depth); }, lds);
     return launch_simt(tile_count, TR_BLOCK, [&] { k_first_hit_tiles<0>(e.d, tiles.data(), spp, kf, smp_begin, smp_end, albedo, normal, depth); }, lds);

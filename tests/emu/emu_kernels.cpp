@@ -80,7 +80,8 @@ NOINSTR int emu_profile_dump(const char* path) {
 
 #include "../../tray_rust_amd/csrc/hip/kernels.hip"
 #include "../../tray_rust_amd/csrc/hip/kernel_select.h"   // the library's choice of the instantiation ...
-#include "../../tray_rust_amd/csrc/hip/launch_rules.h"    // ... and its launch rules: the emulation applies them, it has no copy
+#include "../../tray_rust_amd/csrc/hip/launch_rules.h"    // ... its launch rules ...
+#include "../../tray_rust_amd/csrc/hip/scene_plan.h"      // ... and its per-scene decisions: the emulation applies them, it has no copy
 #ifdef TR_SAMPLE_RANGES   // (emu_sample_ranges.cpp) the kernels take a sample range: EMU_RANGE appends it to a call, and only there do the two builds differ
 #define EMU_RANGE(...) , __VA_ARGS__
 #else
@@ -106,36 +107,9 @@ struct EmuScene {
     std::vector<tray::WfInst> wf_insts;
     std::vector<uint8_t> perm_pool;
     uint32_t retraced = 0;   // rays the flat loop handed to trace_bvh
-    uint32_t depth = 0;   // traversal stack entries per lane, as tray_scene_create sizes them (two-level worst case, generous)
+    tr_plan::ScenePlan plan;   // the library's decisions for the scene (scene_plan.h); the LDS layout by lds_layout()
     uint32_t quad_words = 0;   // stack words per lane of the wavefront traversal (node entries are two words, up to three per record)
 };
-
-uint32_t bvh_depth(const TrayBvhNode* nodes, uint32_t n) {
-    uint32_t best = 0;
-    std::vector<std::pair<uint32_t, uint32_t>> st;
-    if (n) st.push_back({0u, 1u});
-    while (!st.empty()) {
-        auto [idx, dep] = st.back();
-        st.pop_back();
-        best = std::max(best, dep);
-        if (idx < n && nodes[idx].count == 0) { st.push_back({idx + 1, dep + 1}); st.push_back({nodes[idx].offset, dep + 1}); }
-    }
-    return best;
-}
-
-// the scene holds an AnimatedMesh: the ANIM = 3 instantiations run (tray_scene_create: TrayDeviceScene::deforming)
-static bool deforming(const TrayFlatScene* f) {
-    for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].geom_type == TRAY_GEOM_ANIMATED_MESH) return true;
-    return false;
-}
-
-// ... or anything that needs ray.time: the ANIM = 1 / 2 instantiations (tray_scene_create: TrayDeviceScene::animated)
-static bool scene_moves(const TrayFlatScene* f) {
-    bool moving = f->camera.animated != 0;
-    for (uint32_t t_ = 0; t_ < f->n_textures; ++t_) moving = moving || f->textures[t_].n_frames >= 2u;   // animated_image needs ray.time
-    for (uint32_t i = 0; i < f->n_instances; ++i) moving = moving || f->instances[i].animated != 0 || f->instances[i].emis_count >= 2;
-    return moving;
-}
 
 void make_scene(const TrayFlatScene* f, EmuScene& e) {
     DevScene& d = e.d;
@@ -167,45 +141,37 @@ void make_scene(const TrayFlatScene* f, EmuScene& e) {
     d.flat_leaves = e.flat_leaves.data(); d.flat_insts = e.flat_insts.data(); d.n_flat_leaves = (uint32_t)e.flat_leaves.size(); d.tri_leaf = e.tri_leaf.data();
     d.retraced = &g_retraced;
     d.mesh_keys = f->mesh_keys; d.key_times = f->key_times;
-    uint32_t mesh_depth = 0;
-    for (uint32_t m = 0; m < f->n_meshes; ++m) mesh_depth = std::max(mesh_depth, bvh_depth(f->mesh_nodes + f->meshes[m].node_offset, f->meshes[m].node_count));
-    e.depth = mesh_depth + bvh_depth(f->top_nodes, f->n_top_nodes) + 8u;
     e.quad_words = 2u * (e.quads.top_pend + e.quads.mesh_pend) + 34u;
+    tr_plan::ScenePlan& p = e.plan;
+    tr_plan::plan_motion(f, p);
+    tr_plan::plan_materials(e.mats, p);
+    tr_plan::plan_light_filter(f, p);
+    p.film_rows_ok = tr_plan::film_rows_ok(f->film);
+    p.wavefront = tr_plan::wavefront(f, e.paired.narrow && e.quads.narrow && e.quads.ordered, p);
+    tr_plan::plan_stacks(f, tr_plan::mesh_depths(f), p);
+}
+
+// the dynamic LDS of the kernels that traverse; coop / film_rows: 0 = without the cooperative small-mesh test / the row-binned film
+void lds_layout(const TrayFlatScene* f, EmuScene& e, bool coop, bool film_rows) {
+    e.d.film_rows = (film_rows && e.plan.film_rows_ok) ? 1u : 0u;
+    tr_plan::plan_lds(f, coop, e.d.film_rows != 0u, e.plan);
+    e.d.coop_offset = e.plan.coop_offset; e.d.win_offset = e.plan.win_offset;
 }
 
 using hip_emu::launch;
 using hip_emu::launch_simt;
 
-// what tray_scene_create decides per scene: lobe feature set of the kernels, row-binned film, cooperative small-mesh test
-int feature_set(const EmuScene& e) {
-    int feat = FEAT_NONE;
-    for (const DevMaterial& dm : e.mats)
-        for (uint32_t l = 0; l < dm.n_lobes && l < 2u; ++l) {
-            const uint32_t k = dm.lobe[l].kind;
-            if (k == LB_MERL) feat |= FEAT_MERL;
-            if (k == LB_MF_TRANS) feat |= FEAT_MF_TRANS;
-            if (k == LB_SPEC_REFL_DIEL || k == LB_SPEC_REFL_COND || k == LB_SPEC_TRANS || k == LB_TS_COND) feat |= FEAT_SPEC;
-        }
-    for (const DevMaterial& dm : e.mats) if (dm.textured || dm.microfacet == TRAY_MF_GGX) return FEAT_ALL | FEAT_TEX;
-    return (feat & FEAT_MF_TRANS) ? FEAT_ALL : feat;
-}
-bool film_rows_ok(const TrayFlatScene* f) {
-    bool ok = f->film.separable != 0 && f->film.filter_h == 2.0f && f->film.inv_h == 0.5f && f->film.filter_pixel_h == 4;
-    for (int y = 0; ok && y < TRAY_FILTER_TABLE_SIZE; ++y)
-        for (int x = 0; x < TRAY_FILTER_TABLE_SIZE; ++x)
-            if (f->film.table[y * TRAY_FILTER_TABLE_SIZE + x] != f->film.table_x[x] * f->film.table_y[y]) { ok = false; break; }
-    return ok;
-}
-
 }  // namespace
 
 extern "C" {
 
-// k_debug_intersect<0> on n rays (what tray_debug_intersect launches)
+// k_debug_intersect on n rays (what tray_debug_intersect launches)
 int emu_debug_intersect(const TrayFlatScene* f, uint32_t n, const TrayRay* rays, TrayHit* hits) {
     EmuScene e;
     make_scene(f, e);
-    if (deforming(f)) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_intersect<3>(e.d, n, rays, hits); });
+    const int anim = e.plan.anim_debug();
+    if (anim == 3) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_intersect<3>(e.d, n, rays, hits); });
+    else if (anim == 2) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_intersect<2>(e.d, n, rays, hits); });
     else launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_intersect<0>(e.d, n, rays, hits); });
     return 0;
 }
@@ -217,9 +183,9 @@ int emu_debug_sample_radiance(const TrayFlatScene* f, uint32_t n, const uint32_t
     EmuScene e;
     make_scene(f, e);
     const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
-    const bool moving = scene_moves(f);
-    if (deforming(f)) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<3>(e.d, n, px, py, si, spp, kf, out); });
-    else if (moving) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<2>(e.d, n, px, py, si, spp, kf, out); });
+    const int anim = e.plan.anim_debug();
+    if (anim == 3) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<3>(e.d, n, px, py, si, spp, kf, out); });
+    else if (anim == 2) launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<2>(e.d, n, px, py, si, spp, kf, out); });
     else launch((n + TR_BLOCK - 1) / TR_BLOCK, TR_BLOCK, [&] { k_debug_sample_radiance<0>(e.d, n, px, py, si, spp, kf, out); });
     return 0;
 }
@@ -232,7 +198,6 @@ static int render_sampler(const TrayFlatScene* f, const uint32_t* tiles_xy, uint
     EmuScene e;
     make_scene(f, e);
     const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
-    const bool moving = scene_moves(f);
     std::vector<uint2> tiles(tile_count);
     for (uint32_t i = 0; i < tile_count; ++i) tiles[i] = make_uint2(tiles_xy[2 * i], tiles_xy[2 * i + 1]);
     DevStats stats;
@@ -255,7 +220,7 @@ static int render_sampler(const TrayFlatScene* f, const uint32_t* tiles_xy, uint
             tr_rules::sampler_round(sp, j, smp_end ? smp_end - smp_begin : 0u);
             const uint32_t group = tr_rules::sampler_group(sp.count, SP_GROUP_MAX);
             const uint32_t grid = (n_items + group - 1u) / group;
-            select_sampler_pass(deforming(f) ? 3 : moving ? 2 : 0, sampler_lean(feature_set(e), f->integrator), [&](auto kernel) {
+            select_sampler_pass(e.plan.anim_debug(), sampler_lean(e.plan.feat, f->integrator), [&](auto kernel) {
                 rc = launch_simt(grid, TR_BLOCK, [&] { kernel(e.d, tiles.data(), item0, n_items, chunk, 1u, kf, sp, px_state.data(), px_lum.data(), rgbw, &stats, group EMU_RANGE(smp_begin)); });
             });
             if (rc != 0) return -3;
@@ -412,7 +377,7 @@ struct SparseXfTable {
 };
 
 // The tile worker itself: k_path_tiles<0, FEAT> over `tile_count` tiles of the given Morton queue, launched the way
-// launch_tiles does (feature set, row-binned film and cooperative small-mesh test chosen as tray_scene_create chooses them),
+// launch_tiles does (feature set, light filter, stacks, row-binned film and cooperative small-mesh test are the scene's plan: scene_plan.h),
 // as a SIMT emulation: 256 fibers per workgroup, wave intrinsics and barriers are rendezvous. rgbw is accumulated into.
 // coop / film_rows: -1 = as the library decides, 0 = off. Returns 0, or -3 if a rendezvous could not complete.
 // shard / n_shards / chunk_tiles: the launch tray_render_shard_device makes for one rank (chunks shard, shard + n_shards, ... of chunk_tiles
@@ -421,15 +386,12 @@ static int render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32
                         float* rgbw, uint32_t blocks, int coop, int film_rows, unsigned long long* stats_out, uint32_t shard, uint32_t n_shards, uint32_t chunk_tiles) {
     EmuScene e;
     make_scene(f, e);
-    const bool moving = scene_moves(f);
+    const bool moving = e.plan.animated;
     if (f->n_instances > TR_FLAT_MAX && !moving) return -4;   // the library runs the wavefront schedule for those
-    uint32_t n_moving = 0;
-    for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].animated) ++n_moving;
-    std::vector<uint32_t> moving_ids(std::max(n_moving, 1u), 0u);
+    const uint32_t n_moving = e.plan.n_moving;
+    const std::vector<uint32_t>& moving_ids = e.plan.moving_ids;
     std::vector<float> xf_cache;
-    if (moving && n_moving) {   // per-path transform cache, one column per thread of the grid (tray_scene_create)
-        for (uint32_t i = 0; i < f->n_instances; ++i)
-            if (f->instances[i].animated && f->instances[i].moving_slot < n_moving) moving_ids[f->instances[i].moving_slot] = i;
+    if (n_moving) {   // per-path transform cache, one column per thread of the grid
         xf_cache.assign((size_t)n_moving * TR_XF_WORDS * blocks * TR_BLOCK, 0.0f);
         e.d.xf_cache = xf_cache.data(); e.d.moving_ids = moving_ids.data(); e.d.n_moving = n_moving; e.d.xf_stride = n_moving; e.d.xf_cache_lanes = blocks * TR_BLOCK;
     }
@@ -438,13 +400,7 @@ static int render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32
         if (!table.build(f, e.d.frame, moving_ids.data(), n_moving, tiles_xy, tile_count, spp, seed)) return -5;
         if (table.data) { e.d.moving_ids = moving_ids.data(); e.d.xf_tab = table.data; e.d.xf_tab_stride = table.stride; }
     }
-    e.d.film_rows = (film_rows != 0 && film_rows_ok(f)) ? 1u : 0u;
-    uint32_t stack_words = e.depth * TR_BLOCK;
-    bool small_mesh = false;
-    for (uint32_t m = 0; m < f->n_meshes; ++m) small_mesh = small_mesh || f->meshes[m].tri_count <= TR_COOP_MAX_TRIS;
-    if (coop != 0 && small_mesh && f->n_instances <= TR_FLAT_MAX) { e.d.coop_offset = stack_words; stack_words += (TR_BLOCK / 64) * TR_COOP_WORDS; }
-    if (e.d.film_rows) { e.d.win_offset = 0u; stack_words = std::max(stack_words, 4u * WIN_PLANE); }   // tray_scene_create: the film window over the stacks ...
-    else { e.d.win_offset = stack_words; stack_words += 4u * WIN_PLANE; }                               // ... or in its own region
+    lds_layout(f, e, coop != 0, film_rows != 0);
     std::vector<uint2> tiles(tile_count);
     for (uint32_t i = 0; i < tile_count; ++i) tiles[i] = make_uint2(tiles_xy[2 * i], tiles_xy[2 * i + 1]);
     const tr_rules::TileWork w = n_shards ? tr_rules::shard_work(tile_count, shard, n_shards, chunk_tiles) : tr_rules::whole_queue(tile_count);   // tray_render_shard_device
@@ -453,20 +409,16 @@ static int render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32
     DevStats stats;
     std::memset(&stats, 0, sizeof stats);
     const uint32_t kf = tr_rules::frame_key(seed, e.d.frame);
-    const int feat = feature_set(e);
+    const int feat = e.plan.feat;
     tr_rules::whole_frame_range(spp, smp_begin, smp_end);
     const uint32_t levels = tr_rules::tile_levels(w.work, blocks, tr_rules::range_samples(spp, smp_begin, smp_end));
     int rc = 0;
-    // tray_scene_create: the instantiation with mis_ray_filter for scenes with a sphere light or specular lobes
-    bool light_filter = (feat & FEAT_SPEC) != 0;
-    for (uint32_t l = 0; l < f->n_lights; ++l)
-        if (f->instances[f->lights[l]].kind != TRAY_INST_POINT_EMITTER && f->instances[f->lights[l]].geom_type == TRAY_GEOM_SPHERE) light_filter = true;
     const auto run = [&](auto kernel) {
         rc = launch_simt(blocks, TR_BLOCK, [&] { kernel(e.d, tiles.data() + w.first, w.work, w.chunk, w.chunk_stride, spp, kf, levels, rgbw, &counter, &stats EMU_RANGE(smp_begin, smp_end)); },
-                         (size_t)stack_words * 4);
+                         e.plan.stack_bytes);
     };
     const bool whitted = e.d.integrator == TRAY_INTEGRATOR_WHITTED;
-    if (moving) select_path_tiles<1>(feat, whitted, light_filter, run); else select_path_tiles<0>(feat, whitted, light_filter, run);
+    if (moving) select_path_tiles<1>(feat, whitted, e.plan.light_filter, run); else select_path_tiles<0>(feat, whitted, e.plan.light_filter, run);
     if (stats_out) { stats_out[0] = stats.samples; stats_out[1] = stats.vertices; stats_out[2] = stats.rays; stats_out[3] = (unsigned long long)feat; }
     return rc;
 }
@@ -485,10 +437,9 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
                             float* rgbw, int trace, uint32_t n_chunks, uint32_t trace_blocks, uint32_t lds_depth, unsigned long long* stats_out) {
     EmuScene e;
     make_scene(f, e);
-    const bool moving = scene_moves(f);
-    uint32_t n_moving = 0;
-    for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].animated) ++n_moving;
-    e.d.film_rows = film_rows_ok(f) ? 1u : 0u;
+    const bool moving = e.plan.animated;
+    const uint32_t n_moving = e.plan.n_moving;
+    e.d.film_rows = e.plan.film_rows_ok ? 1u : 0u;
     tr_rules::whole_frame_range(spp, smp_begin, smp_end);
     const uint32_t n_smp = tr_rules::range_samples(spp, smp_begin, smp_end);
     const uint32_t slice_shift = tr_rules::wf_slice_shift(tile_count, n_chunks, n_smp, 0u);
@@ -497,11 +448,9 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
     const uint32_t n_slots = n_chunks * TR_BLOCK, n_active = n_slots;
     std::vector<float> pool_data((size_t)F_COUNT * n_slots, 0.0f);
     WfPool pool{pool_data.data(), n_slots, wf_seg_cap(n_chunks)};
-    std::vector<uint32_t> moving_ids(std::max(n_moving, 1u), 0u);
+    const std::vector<uint32_t>& moving_ids = e.plan.moving_ids;
     std::vector<float> xf_cache;
-    if (moving && n_moving) {   // per-path transform cache, one column per pool slot (tray_scene_create)
-        for (uint32_t i = 0; i < f->n_instances; ++i)
-            if (f->instances[i].animated && f->instances[i].moving_slot < n_moving) moving_ids[f->instances[i].moving_slot] = i;
+    if (n_moving) {   // per-path transform cache, one column per pool slot
         xf_cache.assign((size_t)n_moving * TR_XF_REC * n_slots, 0.0f);
         e.d.xf_cache = xf_cache.data(); e.d.moving_ids = moving_ids.data(); e.d.n_moving = n_moving; e.d.xf_stride = n_moving; e.d.xf_cache_lanes = n_slots; e.d.xf_aos = 1u;
     }
@@ -529,15 +478,14 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
     if (lds_depth == 0 || lds_depth > full) lds_depth = full;
     trace_blocks = std::max(1u, std::min(trace_blocks, n_chunks));
     std::vector<uint32_t> overflow((size_t)(full + 64u) * trace_blocks * TR_BLOCK, 0u);
-    const size_t fb_lds = (size_t)e.depth * TR_BLOCK * 4;
+    const size_t fb_lds = (size_t)e.plan.depth * TR_BLOCK * 4;
     const size_t dyn_lds = (size_t)lds_depth * TR_BLOCK * 4;
-    const int feat = feature_set(e);
+    const int feat = e.plan.feat;
     // the material sort of the shading stage (default of the library for the compacted schedule; trace == 2 is the slot form without queues)
     if (trace != 0) return -6;
     const bool sorted = !(feat & FEAT_TEX);
     std::vector<uint32_t> kind_queues((size_t)WF_MAT_KINDS * q_cap, 0u);
-    uint32_t kinds_present = 0;
-    for (const DevMaterial& dm : e.mats) kinds_present |= 1u << dm.mat_kind;
+    const uint32_t kinds_present = e.plan.mat_kinds_present;
     const uint64_t max_rounds = (uint64_t)((n_items + n_chunks - 1) / n_chunks) * (((uint64_t)n_smp + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * e.d.max_depth + 3) + 4) + 32;
     int rc = 0;
     uint64_t rounds = 0;
@@ -654,10 +602,7 @@ int emu_film_splat(const TrayFilm* film, int mode, uint32_t tx, uint32_t ty, uin
     d.filter_w = film->filter_w; d.filter_h = film->filter_h; d.inv_w = film->inv_w; d.inv_h = film->inv_h;
     d.fpw = film->filter_pixel_w; d.fph = film->filter_pixel_h;
     d.filter_table = film->table; d.filter_x = film->table_x; d.filter_y = film->table_y;
-    TrayFlatScene fs;
-    std::memset(&fs, 0, sizeof fs);
-    fs.film = *film;
-    if ((mode == 2 || mode == 3) && !film_rows_ok(&fs)) return 1;
+    if ((mode == 2 || mode == 3) && !tr_plan::film_rows_ok(*film)) return 1;
     const int W = (int)film->width, H = (int)film->height, x0 = (int)tx * 8, y0 = (int)ty * 8;
     const size_t guard = 4096;
     std::vector<float> img((size_t)W * H * 4, 0.0f), win(guard + 4 * WIN_PLANE + guard, 0.0f), gwin(guard + 4 * SP_WIN_MAX * SP_WIN_MAX + guard, 0.0f);
@@ -731,6 +676,19 @@ int emu_film_splat(const TrayFilm* film, int mode, uint32_t tx, uint32_t ty, uin
 
 }  // extern "C"
 
+// The scene's plan (scene_plan.h) as the emulation applies it, for tests/test_scene_plan.py: its scalar fields in the order of tests/_emu.py's PLAN_FIELDS,
+// then the constants the layout is made of. coop / film_rows as for emu_render_tiles.
+extern "C" int emu_scene_plan(const TrayFlatScene* f, int coop, int film_rows, uint32_t* out) {
+    EmuScene e;
+    make_scene(f, e);
+    lds_layout(f, e, coop != 0, film_rows != 0);
+    const tr_plan::ScenePlan& p = e.plan;
+    const uint32_t fields[] = {p.deforming, p.animated, (uint32_t)p.anim_debug(), (uint32_t)p.feat, p.light_filter, p.mat_kinds_present, p.film_rows_ok, p.wavefront,
+                               p.mesh_depth, p.depth, p.coop_offset, p.win_offset, p.stack_bytes, p.n_moving, p.xf_movable,
+                               TR_BLOCK, TR_COOP_MAX_TRIS, TR_COOP_WORDS, TR_FLAT_MAX, WIN_PLANE};
+    std::memcpy(out, fields, sizeof fields);
+    return 0;
+}
 // The device order of the trees and the wavefront traversal's instance records, as tray_scene_create uploads them (host/gates.hpp), for
 // tests/test_device_tree_order.py. Two calls: with null outputs the counts come back (top nodes, mesh nodes, meshes, records).
 extern "C" int emu_device_trees(const TrayFlatScene* f, uint32_t* counts, TrayBvhNode* top, TrayBvhNode* mesh, TrayMesh* meshes, void* wf_insts, int* narrow) {

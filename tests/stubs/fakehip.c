@@ -8,7 +8,8 @@
  * FAKEHIP_FREE_BYTES (what hipMemGetInfo reports free), FAKEHIP_MALLOC_MAX (hipMalloc refuses anything larger) and FAKEHIP_WF_DONE (a 4-byte
  * device-to-host copy -- the wavefront schedule's "tiles done" poll -- reads UINT32_MAX, so that a launch of kernels that do nothing ends).
  * A launch is logged by the library its kernel lives in (dladdr of the host stub): "guide" / "denoise" / "noise ... kernel=<symbol>" for the
- * add-on libraries (tests/test_guide_stub.py, test_denoise_stub.py, test_noise_target_stub.py), "launch" for everything else; under
+ * add-on libraries (tests/test_guide_stub.py, test_denoise_stub.py, test_noise_target_stub.py), "launch ... lds=<dynamic LDS bytes> kernel=<symbol>" for
+ * everything else (tests/test_scene_plan_stub.py); under
  * FAKEHIP_TILE_KERNEL=1 a "range dev=.. begin=.. end=.." line goes in front of the tile kernel's "launch" line (tests/test_sample_ranges_stub.py).
  * A new add-on library gets a branch of its own in hipLaunchKernel. tests/_stub.py builds and preloads this file. */
 #define _GNU_SOURCE
@@ -90,7 +91,6 @@ static __thread struct { dim3 g, b; size_t sh; hipStream_t st; } t_cfg;
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t st) { t_cfg.g = g; t_cfg.b = b; t_cfg.sh = sh; t_cfg.st = st; return 0; }
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* st) { *g = t_cfg.g; *b = t_cfg.b; *sh = t_cfg.sh; *st = t_cfg.st; return 0; }
 hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** args, size_t sh, hipStream_t st) {
-    (void)sh;
     Dl_info di;
     const int found = dladdr(f, &di) && di.dli_fname;
     const char* const sym = found && di.dli_sname ? di.dli_sname : "?";
@@ -125,6 +125,6 @@ hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** args, size_t sh
         film[0] += (float)(t_device + 1);
         logf_("range dev=%d begin=%u end=%u", t_device, ranged ? *(uint32_t*)args[11] : 0u, ranged ? *(uint32_t*)args[12] : 0u);
         logf_("launch dev=%d grid=%u block=%u stream=%p tile_count=%u chunk=%u chunk_stride=%u spp=%u film=%p", t_device, g.x, b.x, st, tile_count, chunk, chunk_stride, spp, (void*)film);
-    } else logf_("launch dev=%d grid=%u block=%u stream=%p", t_device, g.x, b.x, st);
+    } else logf_("launch dev=%d grid=%u block=%u stream=%p lds=%zu kernel=%s", t_device, g.x, b.x, st, sh, sym);
     return 0;
 }

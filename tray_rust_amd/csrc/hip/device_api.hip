@@ -4,6 +4,7 @@
 // kernel_group.hip (kernel_list.h) -- this translation unit only DECLARES them, so a change here recompiles no kernel.
 #include "kernels.hip"
 #include <cmath>
+#include <memory>
 #define TR_INST_EXTERN   // explicit instantiation declarations of every kernel the launch sites below name
 #include "kernel_list.h"
 #include "kernel_select.h"   // (after the declarations: the selectors instantiate no kernel here)
@@ -16,6 +17,7 @@
 #include "first_hit.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
+#include "scene_plan.h"
 
 
 #ifndef WF_PIPES_MAX
@@ -447,169 +449,119 @@ static bool lb_fit(TrayDeviceScene* s) {
     return keep_pool;
 }
 
-static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDeviceScene** out) {
-    if (!f || !out) { set_error("tray_scene_create: null argument"); return TRAY_E_INVALID; }
-    *out = nullptr;
-    if (f->abi_version != TRAY_ABI_VERSION) { set_error("tray_scene_create: ABI version mismatch"); return TRAY_E_INVALID; }
-    if (f->n_lights == 0) { set_error("At least one light is required"); return TRAY_E_INVALID; }   // multithreaded.rs:39
-    // (a frame update that keeps the device's trees never reads the new scene's BVH<Triangle> nodes: they are walked below only if it does not)
-    if (const std::string bad = tray::validate_flat_scene(f, donor == nullptr); !bad.empty()) { set_error("tray_scene_create: inconsistent scene: " + bad); return TRAY_E_INVALID; }
-    if (f->film.width % 8 != 0 || f->film.height % 8 != 0 || f->film.width == 0 || f->film.height == 0) {
-        set_error("Image dimensions not evenly divided by blocks of (8, 8)");
-        return TRAY_E_INVALID;
-    }
-    // the film windows (WIN_MAX, ROW_W, SP_WIN_MAX) hold a tile's write range with a 4-pixel halo: filter widths below 2.5. Every device
-    // film writes within the write range of the sample's tile (kernels.hip: film_admit), so any width with floor(2 w) <= 4 fits.
-    if (f->film.filter_pixel_w > 4 || f->film.filter_pixel_h > 4 || f->film.filter_pixel_w < 0 || f->film.filter_pixel_h < 0) {
-        set_error("reconstruction filters of width or height 2.5 and more are not supported by the LDS film window");
-        return TRAY_E_UNSUPPORTED;
-    }
-    if (f->integrator > TRAY_INTEGRATOR_WHITTED) { set_error("unknown integrator"); return TRAY_E_INVALID; }
-    if (f->integrator == TRAY_INTEGRATOR_WHITTED && f->max_depth > WH_MAX_DEPTH) { set_error("whitted recursion depth > 16 is not supported"); return TRAY_E_UNSUPPORTED; }
-    if (f->integrator != TRAY_INTEGRATOR_WHITTED && f->max_depth > 15) { set_error("pathtracer max_depth > 15 is not supported"); return TRAY_E_UNSUPPORTED; }
-    auto stack_ok = [&](uint32_t first, uint32_t count, bool moving) {   // spline stacks the device evaluates per ray
-        if ((uint64_t)first + count > f->n_xf_levels) return false;
-        for (uint32_t l = 0; moving && l < count; ++l) {
-            const TrayXformLevel& lv = f->xf_levels[first + l];
-            if (lv.kf_count < 2) continue;
-            if (lv.degree > 3 || lv.knot_count != lv.kf_count + lv.degree + 1 || (uint64_t)lv.kf_first + lv.kf_count > f->n_keyframes ||
-                (uint64_t)lv.knot_first + lv.knot_count > f->n_knots) return false;
-        }
-        return true;
-    };
-    if (!stack_ok(f->camera.xf_first, f->camera.xf_count, f->camera.animated != 0)) {
-        set_error("camera keyframes: the device evaluates B-splines of degree <= 3 with consistent knot vectors"); return TRAY_E_UNSUPPORTED;
-    }
-    bool deforming = false;
-    bool moving = f->camera.animated != 0;
-    for (uint32_t i = 0; i < f->n_instances; ++i) {
-        const TrayInstance& in = f->instances[i];
-        if (!stack_ok(in.xf_first, in.xf_count, in.animated != 0)) {
-            set_error("instance keyframes: the device evaluates B-splines of degree <= 3 with consistent knot vectors"); return TRAY_E_UNSUPPORTED;
-        }
-        if (in.emis_count && (uint64_t)in.emis_first + in.emis_count > f->n_color_keys) { set_error("instance references missing colour keys"); return TRAY_E_INVALID; }
-        moving = moving || in.animated != 0 || in.emis_count >= 2;
-        if (in.kind != TRAY_INST_POINT_EMITTER && in.material_id >= f->n_materials) { set_error("instance references a missing material"); return TRAY_E_INVALID; }
-        if ((in.geom_type == TRAY_GEOM_MESH || in.geom_type == TRAY_GEOM_ANIMATED_MESH) && in.mesh_id >= f->n_meshes) { set_error("instance references a missing mesh"); return TRAY_E_INVALID; }
-        if (in.geom_type == TRAY_GEOM_ANIMATED_MESH) { deforming = true; moving = true; }
-    }
-    TrayDeviceScene* s = new TrayDeviceScene();
-    s->deforming = deforming;
-    s->identity = scene_identity(f);
-    s->device = donor ? donor->device : g_device;
-    s->donor = donor;
-    if (hipSetDevice(s->device) != hipSuccess) { delete s; set_error("hipSetDevice failed (is a GPU present?)"); return TRAY_E_DEVICE; }
-    DevScene& d = s->dev;
-    int rc = TRAY_OK;
-    const TrayInstance* d_inst = nullptr;
-#define UP_(field, hostptr, count, unchanged)                                         \
-    if (rc == TRAY_OK) {                                                              \
-        std::remove_cv_t<std::remove_pointer_t<decltype(hostptr)>> const* _p = nullptr; \
-        rc = upload(s, #field, unchanged, hostptr, (size_t)(count), &_p);             \
-        d.field = _p;                                                                 \
-    }
-#define UP(field, hostptr, count) UP_(field, hostptr, count, false)    /* may differ from frame to frame */
-#define UPS(field, hostptr, count) UP_(field, hostptr, count, true)    /* part of the scene, the same at every frame */
-    if (rc == TRAY_OK) rc = upload(s, "instances", false, f->instances, f->n_instances, &d_inst);
-    d.instances = d_inst;
-    s->d_instances = const_cast<TrayInstance*>(d_inst);
-    // the trees in device order (host/gates.hpp: sibling pairs); the BVH<Triangle>s are part of the scene, a frame update keeps the donor's
-    tray::PairedTrees paired;
-    size_t n_paired = 0;   // nodes of the BVH<Triangle>s in device order: one more per tree
-    for (uint32_t m = 0; m < f->n_meshes; ++m) n_paired += f->meshes[m].node_count ? f->meshes[m].node_count + 1u : 0u;
-    bool keep_trees = false;
-    const size_t top_quad_cap = 2u * (size_t)f->n_instances + 2u;   // records a BVH<Instance> of this scene can need (one per interior node + the entry)
+// The trees of a scene in device order and what a frame update keeps of the donor's: host bookkeeping, nothing is uploaded here
+struct SceneTrees {
+    tray::PairedTrees paired;   // sibling pairs (host/gates.hpp); the BVH<Triangle>s are part of the scene, a frame update keeps the donor's
+    tray::QuadTrees quads;      // the same trees as 128-byte records of two levels each, for the wavefront traversal (host/gates.hpp: QuadTrees)
+    bool keep = false;
+    size_t n_paired = 0;        // nodes of the BVH<Triangle>s in device order: one more per tree
+    size_t top_quad_cap = 0;    // records a BVH<Instance> of this scene can need (one per interior node + the entry)
+};
+static int scene_trees(const TrayFlatScene* f, TrayDeviceScene* s, SceneTrees& t) {
+    const TrayDeviceScene* donor = s->donor;
+    for (uint32_t m = 0; m < f->n_meshes; ++m) t.n_paired += f->meshes[m].node_count ? f->meshes[m].node_count + 1u : 0u;
+    t.top_quad_cap = 2u * (size_t)f->n_instances + 2u;
     if (donor && donor->quad_first.size() == f->n_meshes) {
         bool have_pairs = false, have_quads = false;
         for (const TrayDevBuf& b : donor->bufs) {
-            have_pairs = have_pairs || (std::strcmp(b.key, "mesh_nodes") == 0 && b.bytes == std::max<size_t>(n_paired, 1) * sizeof(TrayBvhNode));
-            have_quads = have_quads || (std::strcmp(b.key, "quads") == 0 && b.bytes == (donor->n_mesh_quads + top_quad_cap) * sizeof(tray::QuadNode));
+            have_pairs = have_pairs || (std::strcmp(b.key, "mesh_nodes") == 0 && b.bytes == std::max<size_t>(t.n_paired, 1) * sizeof(TrayBvhNode));
+            have_quads = have_quads || (std::strcmp(b.key, "quads") == 0 && b.bytes == (donor->n_mesh_quads + t.top_quad_cap) * sizeof(tray::QuadNode));
         }
-        keep_trees = have_pairs && have_quads;
+        t.keep = have_pairs && have_quads;
     }
-    if (rc == TRAY_OK && donor && !keep_trees) {
-        if (const std::string bad = tray::validate_mesh_trees(f); !bad.empty()) { rc = TRAY_E_INVALID; set_error("tray_scene_update_frame: inconsistent scene: " + bad); }
+    if (donor && !t.keep)
+        if (const std::string bad = tray::validate_mesh_trees(f); !bad.empty()) { set_error("tray_scene_update_frame: inconsistent scene: " + bad); return TRAY_E_INVALID; }
+    if (!tray::pair_trees(f, t.paired, t.keep)) { set_error("BVH arrays do not describe trees"); return TRAY_E_INVALID; }
+    uint32_t bfs_levels = TRAY_QUAD_BFS_LEVELS;
+    if (const char* e = getenv("TRAYHIP_QUAD_BFS")) bfs_levels = (uint32_t)std::max(0, atoi(e));
+    tray::quad_trees(f, t.quads, t.keep, bfs_levels);
+    s->narrow_trees = (t.keep ? donor->narrow_trees : t.paired.narrow) && t.quads.narrow;
+    s->ordered_boxes = (t.keep ? donor->ordered_boxes : true) && t.quads.ordered;
+    s->paired_meshes = t.keep ? donor->paired_meshes : t.paired.meshes;
+    s->quad_first = t.keep ? donor->quad_first : t.quads.mesh_first;
+    s->n_mesh_quads = t.keep ? donor->n_mesh_quads : t.quads.mesh.size();
+    s->quad_mesh_pend = t.keep ? donor->quad_mesh_pend : t.quads.mesh_pend;
+    // per lane: node entries are two words (descriptor, entry distance); the instances of a BVH<Instance> leaf (<= 31) and the
+    // exit-mesh sentinel one each; rounded up so that consecutive frames of a sequence keep the pool's overflow columns
+    s->quad_stack_words = (2u * (t.quads.top_pend + s->quad_mesh_pend) + 32u + 2u + 15u) / 16u * 16u;
+    if (t.quads.top.size() > t.top_quad_cap || (s->n_mesh_quads + t.top_quad_cap) * sizeof(tray::QuadNode) >= ((size_t)1 << 32)) {
+        set_error("the quad records of the scene's trees do not fit 32-bit offsets"); return TRAY_E_UNSUPPORTED;
     }
-    if (rc == TRAY_OK && !tray::pair_trees(f, paired, keep_trees)) { rc = TRAY_E_INVALID; set_error("BVH arrays do not describe trees"); }
-    s->narrow_trees = keep_trees ? donor->narrow_trees : paired.narrow;
-    s->paired_meshes = keep_trees ? donor->paired_meshes : paired.meshes;
-    // the same trees as 128-byte records of two levels each, for the wavefront traversal (host/gates.hpp: QuadTrees)
-    tray::QuadTrees quads;
-    if (rc == TRAY_OK) {
-        uint32_t bfs_levels = TRAY_QUAD_BFS_LEVELS;
-        if (const char* e = getenv("TRAYHIP_QUAD_BFS")) bfs_levels = (uint32_t)std::max(0, atoi(e));
-        tray::quad_trees(f, quads, keep_trees, bfs_levels);
-        s->narrow_trees = s->narrow_trees && quads.narrow;
-        s->ordered_boxes = (keep_trees ? donor->ordered_boxes : true) && quads.ordered;
-        s->quad_first = keep_trees ? donor->quad_first : quads.mesh_first;
-        s->n_mesh_quads = keep_trees ? donor->n_mesh_quads : quads.mesh.size();
-        s->quad_mesh_pend = keep_trees ? donor->quad_mesh_pend : quads.mesh_pend;
-        // per lane: node entries are two words (descriptor, entry distance); the instances of a BVH<Instance> leaf (<= 31) and the
-        // exit-mesh sentinel one each; rounded up so that consecutive frames of a sequence keep the pool's overflow columns
-        s->quad_stack_words = (2u * (quads.top_pend + s->quad_mesh_pend) + 32u + 2u + 15u) / 16u * 16u;
+    // (a frame update that keeps the device's trees keeps their depths: tr_plan::mesh_depths)
+    s->mesh_depths = t.keep && donor->mesh_depths.size() == f->n_meshes ? donor->mesh_depths : tr_plan::mesh_depths(f);
+    return TRAY_OK;
+}
+
+// The decisions of scene_plan.h for this scene, with the environment's overrides, into the device scene
+static int scene_plan(const TrayFlatScene* f, TrayDeviceScene* s, const std::vector<DevMaterial>& mats, tr_plan::ScenePlan& p) {
+    tr_plan::plan_motion(f, p);
+    if (p.n_moving > 64) { set_error("more than 64 instances move within one frame: the per-path transform cache does not cover that"); return TRAY_E_UNSUPPORTED; }
+    tr_plan::plan_materials(mats, p);
+    if (getenv("TRAYHIP_FEAT_ALL")) p.feat |= FEAT_ALL;
+    tr_plan::plan_light_filter(f, p);
+    if (getenv("TRAYHIP_NO_LIGHT_FILTER")) p.light_filter = false;
+    p.film_rows_ok = tr_plan::film_rows_ok(f->film);
+    s->dev.film_rows = (p.film_rows_ok && !getenv("TRAYHIP_DIRECT_FILM")) ? 1u : 0u;
+    p.wavefront = tr_plan::wavefront(f, s->narrow_trees && s->ordered_boxes, p);
+    if (const char* m = getenv("TRAYHIP_MODE")) p.wavefront = std::string(m) == "wave" && tr_plan::wavefront_can(f, p);   // (whatever the instance count and the trees)
+    tr_plan::plan_stacks(f, s->mesh_depths, p);
+    if (p.depth > 96) { set_error("BVH too deep for the LDS traversal stack (" + std::to_string(p.depth) + " levels)"); return TRAY_E_UNSUPPORTED; }
+    if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] traversal stack: %u entries per lane (deepest BVH<Triangle> %u)\n", p.depth, p.mesh_depth);
+    tr_plan::plan_lds(f, !getenv("TRAYHIP_NO_COOP"), s->dev.film_rows != 0u, p);
+    s->deforming = p.deforming; s->animated = p.animated; s->deferred_n_moving = p.n_moving; s->xf_movable = p.xf_movable;
+    s->feat = p.feat; s->light_filter = p.light_filter; s->mat_kinds_present = p.mat_kinds_present; s->wavefront = p.wavefront;
+    s->stack_bytes = p.stack_bytes; s->dev.coop_offset = p.coop_offset; s->dev.win_offset = p.win_offset;
+    // ray binning before the traversal stages (wavefront.h): the cells are those of the frame's BVH<Instance> root box
+    s->bin_grid = f->n_top_nodes ? wf_bin_grid(f->top_nodes[0].bmin, f->top_nodes[0].bmax) : WfBinGrid{};
+    s->wf_bin_stages = WF_BIN_DEFAULT;
+    if (const char* e = getenv("TRAYHIP_WF_BIN")) s->wf_bin_stages = (uint32_t)std::max(0, atoi(e)) & 3u;
+    s->wf_fused = WF_FUSED_DEFAULT != 0;
+    if (const char* e = getenv("TRAYHIP_WF_FUSED")) s->wf_fused = atoi(e) != 0;
+    return TRAY_OK;
+}
+
+// The scene's device buffers (a frame update takes the donor's where upload() finds them) and the DevScene that points to them
+static int scene_upload(const TrayFlatScene* f, TrayDeviceScene* s, const SceneTrees& t, const std::vector<DevMaterial>& mats, const tr_plan::ScenePlan& p) {
+    DevScene& d = s->dev;
+    int rc = TRAY_OK;
+#define UP_(field, key, hostptr, count, unchanged)                                    \
+    if (rc == TRAY_OK) {                                                              \
+        std::remove_cv_t<std::remove_pointer_t<decltype(hostptr)>> const* _p = nullptr; \
+        rc = upload(s, key, unchanged, hostptr, (size_t)(count), &_p);                \
+        field = const_cast<std::remove_reference_t<decltype(field)>>(_p);             \
     }
+#define UP(field, hostptr, count) UP_(d.field, #field, hostptr, count, false)    /* may differ from frame to frame */
+#define UPS(field, hostptr, count) UP_(d.field, #field, hostptr, count, true)    /* part of the scene, the same at every frame */
+    UP(instances, f->instances, f->n_instances)
+    s->d_instances = const_cast<TrayInstance*>(d.instances);
     {   // the wavefront traversal's instance records (host/gates.hpp): per frame, as the instances are
         std::vector<tray::WfInst> recs;
         tray::wf_inst_records(f, s->quad_first, recs);
         UP(wf_insts, recs.data(), recs.size())
     }
-    UP(top_nodes, paired.top.data(), paired.top.size())
-    if (rc == TRAY_OK && (quads.top.size() > top_quad_cap || (s->n_mesh_quads + top_quad_cap) * sizeof(tray::QuadNode) >= ((size_t)1 << 32))) {
-        rc = TRAY_E_UNSUPPORTED; set_error("the quad records of the scene's trees do not fit 32-bit offsets");
-    }
+    UP(top_nodes, t.paired.top.data(), t.paired.top.size())
     if (rc == TRAY_OK) {   // one buffer: the BVH<Triangle>s (kept across frames), then this frame's BVH<Instance>
         const tray::QuadNode* dq = nullptr;
         std::vector<tray::QuadNode> all;
-        if (!keep_trees) {
-            all = quads.mesh;
-            all.insert(all.end(), quads.top.begin(), quads.top.end());
-            all.resize(s->n_mesh_quads + top_quad_cap, tray::quad_empty_record());
+        if (!t.keep) {
+            all = t.quads.mesh;
+            all.insert(all.end(), t.quads.top.begin(), t.quads.top.end());
+            all.resize(s->n_mesh_quads + t.top_quad_cap, tray::quad_empty_record());
         }
-        rc = upload(s, "quads", keep_trees, keep_trees ? static_cast<const tray::QuadNode*>(nullptr) : all.data(), s->n_mesh_quads + top_quad_cap, &dq);
-        if (rc == TRAY_OK && keep_trees && hipMemcpy(const_cast<tray::QuadNode*>(dq) + s->n_mesh_quads, quads.top.data(), quads.top.size() * sizeof(tray::QuadNode), hipMemcpyHostToDevice) != hipSuccess) {
+        rc = upload(s, "quads", t.keep, t.keep ? static_cast<const tray::QuadNode*>(nullptr) : all.data(), s->n_mesh_quads + t.top_quad_cap, &dq);
+        if (rc == TRAY_OK && t.keep && hipMemcpy(const_cast<tray::QuadNode*>(dq) + s->n_mesh_quads, t.quads.top.data(), t.quads.top.size() * sizeof(tray::QuadNode), hipMemcpyHostToDevice) != hipSuccess) {
             rc = TRAY_E_DEVICE; set_error("hipMemcpy of the BVH<Instance> records failed");
         }
         d.quads = reinterpret_cast<const float4*>(dq);
         d.top_quad_first = (uint32_t)s->n_mesh_quads;
     }
-    {   // ray binning before the traversal stages (wavefront.h): the cells are those of the frame's BVH<Instance> root box
-        s->bin_grid = f->n_top_nodes ? wf_bin_grid(f->top_nodes[0].bmin, f->top_nodes[0].bmax) : WfBinGrid{};
-        s->wf_bin_stages = WF_BIN_DEFAULT;
-        if (const char* e = getenv("TRAYHIP_WF_BIN")) s->wf_bin_stages = (uint32_t)std::max(0, atoi(e)) & 3u;
-        s->wf_fused = WF_FUSED_DEFAULT != 0;
-        if (const char* e = getenv("TRAYHIP_WF_FUSED")) s->wf_fused = atoi(e) != 0;
-    }
     UP(top_order, f->top_order, f->n_top_order)
-    UPS(meshes, keep_trees ? f->meshes : paired.meshes.data(), f->n_meshes)          // (kept: the donor's copies are not written)
-    UPS(mesh_nodes, keep_trees ? f->mesh_nodes : paired.mesh.data(), n_paired)
+    UPS(meshes, t.keep ? f->meshes : t.paired.meshes.data(), f->n_meshes)          // (kept: the donor's copies are not written)
+    UPS(mesh_nodes, t.keep ? f->mesh_nodes : t.paired.mesh.data(), t.n_paired)
     UPS(tri_verts, f->tri_verts, f->n_tris)
     UPS(tri_attrs, f->tri_attrs, f->n_tris)
     UPS(mesh_keys, f->mesh_keys, f->n_mesh_keys)      // (AnimatedMesh: keyframe counts and times; read by the ANIM = 3 kernels only)
     UPS(key_times, f->key_times, f->n_key_times)
-    std::vector<DevMaterial> mats(f->n_materials);
-    for (uint32_t i = 0; i < f->n_materials; ++i) {
-        if (f->materials[i].kind == TRAY_MAT_MERL && f->materials[i].table >= f->n_merl) { rc = TRAY_E_INVALID; set_error("material references a missing MERL table"); }
-        else mats[i] = lower_material(f->materials[i], f->merl_tables);
-    }
-    {   // smallest kernel feature set that covers the materials
-        int feat = FEAT_NONE;
-        for (const DevMaterial& dm : mats)
-            for (uint32_t l = 0; l < dm.n_lobes && l < 2u; ++l) {
-                const uint32_t k = dm.lobe[l].kind;
-                if (k == LB_MERL) feat |= FEAT_MERL;
-                if (k == LB_MF_TRANS) feat |= FEAT_MF_TRANS;
-                if (k == LB_SPEC_REFL_DIEL || k == LB_SPEC_REFL_COND || k == LB_SPEC_TRANS || k == LB_TS_COND) feat |= FEAT_SPEC;
-            }
-        s->feat = (feat & FEAT_MF_TRANS) ? FEAT_ALL : feat;
-        if (getenv("TRAYHIP_FEAT_ALL")) s->feat = FEAT_ALL;
-        for (const DevMaterial& dm : mats)   // lobes of textured materials are only known per hit; GGX lives in the same instantiation
-            if (dm.textured || dm.microfacet == TRAY_MF_GGX) s->feat = FEAT_ALL | FEAT_TEX;
-        s->light_filter = (s->feat & FEAT_SPEC) != 0;
-        for (uint32_t l = 0; l < f->n_lights; ++l)
-            if (f->instances[f->lights[l]].kind != TRAY_INST_POINT_EMITTER && f->instances[f->lights[l]].geom_type == TRAY_GEOM_SPHERE) s->light_filter = true;
-        if (getenv("TRAYHIP_NO_LIGHT_FILTER")) s->light_filter = false;
-    }
-    for (const DevMaterial& dm : mats) s->mat_kinds_present |= 1u << dm.mat_kind;
     if (f->n_textures) {
         UPS(textures, f->textures, f->n_textures)
         UPS(tex_frames, f->tex_frames, f->n_tex_frames)
@@ -630,209 +582,100 @@ static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDevic
         perm_pool_build(f->max_depth + 1u, pool.data());
         UPS(perm_pool, pool.data(), pool.size())
     }
-#undef UP
-#undef UPS
-#undef UP_
-    for (uint32_t t = 0; t < f->n_textures; ++t) moving = moving || f->textures[t].n_frames >= 2u;   // animated_image: sampled at ray.time, which only the ANIM kernels carry
-    s->animated = moving;
-    if (rc == TRAY_OK) {   // the flat instance loop's records and gates (host/gates.hpp; dev_geom.h: trace_flat, mesh_leaf_coop)
+    {   // the flat instance loop's records and gates (host/gates.hpp; dev_geom.h: trace_flat, mesh_leaf_coop)
         std::vector<tray::FlatLeaf> leaves;
         std::vector<tray::FlatInst> insts;
         std::vector<uint8_t> tri_leaf;
-        tray::flat_loop_gates(f, paired, TR_COOP_MAX_TRIS, leaves, insts, tri_leaf);
-        const tray::FlatLeaf* d_leaves = nullptr;
-        const tray::FlatInst* d_insts = nullptr;
-        const uint8_t* d_tri_leaf = nullptr;
-        rc = upload(s, "flat_leaves", false, leaves.data(), leaves.size(), &d_leaves);
-        if (rc == TRAY_OK) rc = upload(s, "flat_insts", false, insts.data(), insts.size(), &d_insts);
-        if (rc == TRAY_OK) rc = upload(s, "tri_leaf", true, tri_leaf.data(), tri_leaf.size(), &d_tri_leaf);
-        d.flat_leaves = d_leaves; d.flat_insts = d_insts; d.n_flat_leaves = (uint32_t)leaves.size(); d.tri_leaf = d_tri_leaf;
+        tray::flat_loop_gates(f, t.paired, TR_COOP_MAX_TRIS, leaves, insts, tri_leaf);
+        UP(flat_leaves, leaves.data(), leaves.size())
+        UP(flat_insts, insts.data(), insts.size())
+        UPS(tri_leaf, tri_leaf.data(), tri_leaf.size())
+        d.n_flat_leaves = (uint32_t)leaves.size();
     }
-    if (rc != TRAY_OK) { tray_scene_destroy(s); return rc; }
+    UP_(d.camera_p, "camera", &f->camera, 1, false)
+    s->camera_animated = f->camera.animated != 0;
     s->n_materials = f->n_materials;
     d.n_instances = f->n_instances; d.n_lights = f->n_lights; d.min_depth = f->min_depth; d.max_depth = f->max_depth;
     d.width = f->film.width; d.height = f->film.height; d.frame = f->frame; d.integrator = f->integrator;
-    {   // row-binned film needs: separable table, filter_h == 2 (class = eighth of a pixel), consistent factors
-        bool ok = f->film.separable != 0 && f->film.filter_h == 2.0f && f->film.inv_h == 0.5f && f->film.filter_pixel_h == 4;
-        for (int y = 0; ok && y < TRAY_FILTER_TABLE_SIZE; ++y)
-            for (int x = 0; x < TRAY_FILTER_TABLE_SIZE; ++x)
-                if (f->film.table[y * TRAY_FILTER_TABLE_SIZE + x] != f->film.table_x[x] * f->film.table_y[y]) { ok = false; break; }
-        d.film_rows = (ok && !getenv("TRAYHIP_DIRECT_FILM")) ? 1u : 0u;
-        // schedule: the tile megakernel for scenes its flat instance loop covers, the wavefront stage kernels (compacted ray
-        // queues, persistent traversal with dynamic fetch) for scenes that go through BVH<Instance>; TRAYHIP_MODE overrides
-        s->wavefront = f->n_instances > TR_FLAT_MAX;
-        if (const char* m = getenv("TRAYHIP_MODE")) s->wavefront = std::string(m) == "wave";
-        // a tree the quad-record traversal cannot take (a box with min > max or NaN -- BBox::new() is +inf / -inf in the reference --, a mesh beyond the
-        // 23-bit descriptors) renders through the tile kernel's binary traversal, which is the reference's, instead of failing at render time
-        if (s->wavefront && (!s->narrow_trees || !s->ordered_boxes) && !getenv("TRAYHIP_MODE")) s->wavefront = false;
-        if (f->integrator == TRAY_INTEGRATOR_WHITTED) s->wavefront = false;   // the recursion runs inside the tile kernel only (dev_whitted.h)
-        if (s->deforming) s->wavefront = false;   // (k_sampler_pass<3> renders these scenes: launch_tiles)
-    }
     d.filter_w = f->film.filter_w; d.filter_h = f->film.filter_h; d.inv_w = f->film.inv_w; d.inv_h = f->film.inv_h;
     d.fpw = f->film.filter_pixel_w; d.fph = f->film.filter_pixel_h;
-    {
-        const TrayCamera* d_cam = nullptr;
-        rc = upload(s, "camera", false, &f->camera, 1, &d_cam);
-        d.camera_p = d_cam;
-        s->camera_animated = f->camera.animated != 0;
-        if (rc != TRAY_OK) { tray_scene_destroy(s); return rc; }
-    }
     // Morton tile queue (BlockQueue::new)
-    uint32_t n_tiles = 0;
-    rc = tray_block_queue(d.width, d.height, 0, 0, nullptr, 0, &n_tiles);
-    std::vector<uint32_t> xy(2 * (size_t)n_tiles);
-    if (rc == TRAY_OK) rc = tray_block_queue(d.width, d.height, 0, 0, xy.data(), n_tiles, &n_tiles);
-    const uint2* d_tiles = nullptr;
-    if (rc == TRAY_OK) rc = upload(s, "tiles", true, reinterpret_cast<const uint2*>(xy.data()), n_tiles, &d_tiles);
-    s->d_tiles = const_cast<uint2*>(d_tiles);
-    s->n_tiles = n_tiles;
-    const uint32_t* d_counter = nullptr;
-    const DevStats* d_stats = nullptr;
-    uint32_t zero = 0;
+    if (rc == TRAY_OK) rc = tray_block_queue(d.width, d.height, 0, 0, nullptr, 0, &s->n_tiles);
+    std::vector<uint32_t> xy(2 * (size_t)s->n_tiles);
+    if (rc == TRAY_OK) rc = tray_block_queue(d.width, d.height, 0, 0, xy.data(), s->n_tiles, &s->n_tiles);
+    UP_(s->d_tiles, "tiles", reinterpret_cast<const uint2*>(xy.data()), s->n_tiles, true)
+    const uint32_t zero = 0;
     std::vector<DevStats> zs(WF_STAT_SLOTS);
     std::memset(zs.data(), 0, zs.size() * sizeof(DevStats));
-    if (rc == TRAY_OK) rc = upload(s, "counter", false, &zero, 1, &d_counter);
-    if (rc == TRAY_OK) rc = upload(s, "stats", false, zs.data(), zs.size(), &d_stats);
-    const uint32_t* d_retraced = nullptr;
-    if (rc == TRAY_OK) rc = upload(s, "retraced", false, &zero, 1, &d_retraced);
-    s->d_counter = const_cast<uint32_t*>(d_counter);
-    s->d_stats = const_cast<DevStats*>(d_stats);
-    s->d_retraced = const_cast<uint32_t*>(d_retraced);
+    UP_(s->d_counter, "counter", &zero, 1, false)
+    UP_(s->d_stats, "stats", zs.data(), zs.size(), false)
+    UP_(s->d_retraced, "retraced", &zero, 1, false)
     d.retraced = s->d_retraced;
-    if (rc != TRAY_OK) { tray_scene_destroy(s); return rc; }
+    if (rc == TRAY_OK && p.n_moving) {   // the moving instances of the per-path transform cache (dev_geom.h)
+        UP_(d.moving_ids, "moving_ids", p.moving_ids.data(), p.moving_ids.size(), false)
+        if (rc != TRAY_OK) rc = TRAY_E_NOMEM;
+        d.n_moving = p.n_moving;
+        d.xf_stride = p.n_moving;
+        d.xf_aos = p.wavefront ? 1u : 0u;
+    }
+#undef UP
+#undef UPS
+#undef UP_
+    if (rc != TRAY_OK) return rc;
+    TrayDeviceScene* donor = s->donor;
     if (donor && donor->ev0 && donor->ev1) { s->ev0 = donor->ev0; s->ev1 = donor->ev1; donor->ev0 = nullptr; donor->ev1 = nullptr; }
-    else if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) {
-        tray_scene_destroy(s); set_error("hipEventCreate failed"); return TRAY_E_DEVICE;
-    }
-    {   // traversal stack depth: deepest node of any BVH<Triangle>; the one-loop two-level traversal (more than
-        // TR_FLAT_MAX instances) also keeps the top-level path, the instances of a leaf and a sentinel
-        auto depth_of = [](const TrayBvhNode* nodes, uint32_t n) {
-            uint32_t best = 0;
-            std::vector<std::pair<uint32_t, uint32_t>> st;   // node, depth
-            if (n) st.push_back({0u, 1u});
-            while (!st.empty()) {
-                auto [idx, dep] = st.back();
-                st.pop_back();
-                best = std::max(best, dep);
-                if (idx < n && nodes[idx].count == 0) { st.push_back({idx + 1, dep + 1}); st.push_back({nodes[idx].offset, dep + 1}); }
-            }
-            return best;
-        };
-        // (a frame update that keeps the device's trees keeps their depths: the walk over the 6.2 M nodes of the tr15 stand-in's meshes was 80 ms per frame)
-        std::vector<uint32_t>& mesh_depths = s->mesh_depths;
-        if (keep_trees && donor->mesh_depths.size() == f->n_meshes) mesh_depths = donor->mesh_depths;
-        else {
-            mesh_depths.assign(f->n_meshes, 0u);
-            for (uint32_t m = 0; m < f->n_meshes; ++m) mesh_depths[m] = depth_of(f->mesh_nodes + f->meshes[m].node_offset, f->meshes[m].node_count);
-        }
-        uint32_t mesh_depth = 0;
-        for (uint32_t m = 0; m < f->n_meshes; ++m) mesh_depth = std::max(mesh_depth, mesh_depths[m]);
-        uint32_t depth = mesh_depth + 1;   // per-lane BVH<Triangle> traversal: one pending far child per level
-        {   // (scenes the flat instance loop serves need it too: rays with tied candidates are re-traced through BVH<Instance>)
-            // two-level traversal: exact worst case over the instances. While instance j of a BVH<Instance> leaf at depth d is
-            // traversed the stack holds the pending far children of the top-level path (d - 1), the leaf's later instances,
-            // the exit-mesh sentinel and the pending far children inside the mesh (its depth - 1).
-            uint32_t worst = 0;
-            std::vector<std::pair<uint32_t, uint32_t>> st;
-            if (f->n_top_nodes) st.push_back({0u, 1u});
-            while (!st.empty()) {
-                auto [idx, dep] = st.back();
-                st.pop_back();
-                if (idx >= f->n_top_nodes) continue;
-                const TrayBvhNode& nd = f->top_nodes[idx];
-                if (nd.count == 0) { st.push_back({idx + 1, dep + 1}); st.push_back({nd.offset, dep + 1}); continue; }
-                for (uint32_t j = 0; j < nd.count; ++j) {
-                    uint32_t need = (dep - 1) + (nd.count - 1 - j);
-                    if (nd.offset + j < f->n_top_order) {
-                        const TrayInstance& in = f->instances[f->top_order[nd.offset + j]];
-                        if ((in.geom_type == TRAY_GEOM_MESH || in.geom_type == TRAY_GEOM_ANIMATED_MESH) && in.mesh_id < f->n_meshes) need += 1 + (mesh_depths[in.mesh_id] > 0 ? mesh_depths[in.mesh_id] - 1 : 0);
-                    }
-                    worst = std::max(worst, need);
-                }
-                worst = std::max(worst, dep - 1 + nd.count);   // right after the leaf queued its instances
-            }
-            depth = std::max(depth, worst + 1);   // + 1 spare entry
-        }
-        depth = std::max(depth, 4u);
-        if (depth > 96) { tray_scene_destroy(s); set_error("BVH too deep for the LDS traversal stack (" + std::to_string(depth) + " levels)"); return TRAY_E_UNSUPPORTED; }
-        s->stack_bytes = depth * TR_BLOCK * (uint32_t)sizeof(uint32_t);
-        if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] traversal stack: %u entries per lane (deepest BVH<Triangle> %u)\n", depth, mesh_depth);
-        // cooperative test of small meshes (dev_geom.h: mesh_leaf_coop) in the flat instance loop: per-wave LDS behind the stacks
-        bool single_leaf = false;
-        for (uint32_t m = 0; m < f->n_meshes; ++m) single_leaf = single_leaf || f->meshes[m].tri_count <= TR_COOP_MAX_TRIS;
-        if (single_leaf && !s->wavefront && f->n_instances <= TR_FLAT_MAX && !getenv("TRAYHIP_NO_COOP")) {   // (moving scenes too: the flat loop serves them since round 4)
-            s->dev.coop_offset = depth * TR_BLOCK;
-            s->stack_bytes += (TR_BLOCK / 64) * TR_COOP_WORDS * (uint32_t)sizeof(float);
-        }
-        {   // the tile kernel's film window: over the stacks for the row-binned film, behind everything else otherwise (k_path_tiles)
-            const uint32_t win_bytes = 4u * WIN_PLANE * (uint32_t)sizeof(float);
-            if (d.film_rows) { s->dev.win_offset = 0u; s->stack_bytes = std::max(s->stack_bytes, win_bytes); }
-            else { s->dev.win_offset = s->stack_bytes / (uint32_t)sizeof(uint32_t); s->stack_bytes += win_bytes; }
-        }
-        if (s->stack_bytes > 32u * 1024u) {   // past the default dynamic-LDS window: raise the per-kernel limit (160 KB LDS per CU)
-            const int bytes = (int)s->stack_bytes;
-            const void* const traversing[] = {   // every kernel that is launched with s->stack_bytes (or its LDS part)
-                reinterpret_cast<const void*>(k_path_tiles<0, FEAT_NONE>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL>),
-                reinterpret_cast<const void*>(k_path_tiles<0, FEAT_SPEC>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL | FEAT_SPEC>),
-                reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL>),
-                reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX>),
-                reinterpret_cast<const void*>(k_path_tiles<1, FEAT_NONE>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL>),
-                reinterpret_cast<const void*>(k_path_tiles<1, FEAT_SPEC>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL | FEAT_SPEC>),
-                reinterpret_cast<const void*>(k_path_tiles<0, FEAT_NONE, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL | FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_PATH, true>),
-                reinterpret_cast<const void*>(k_path_tiles<1, FEAT_NONE, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL | FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_PATH, true>),
-                reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>),
-                reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>),
-                reinterpret_cast<const void*>(k_wf_trace_dyn<0, 0>), reinterpret_cast<const void*>(k_wf_trace_dyn<0, 1>),
-                reinterpret_cast<const void*>(k_wf_trace_dyn<1, 0>), reinterpret_cast<const void*>(k_wf_trace_dyn<1, 1>),
-                reinterpret_cast<const void*>(k_wf_trace_dyn<2, 0>), reinterpret_cast<const void*>(k_wf_trace_dyn<2, 1>),
-                reinterpret_cast<const void*>(k_wf_trace_fallback<0, 0>), reinterpret_cast<const void*>(k_wf_trace_fallback<0, 1>),
-                reinterpret_cast<const void*>(k_wf_trace_fallback<1, 0>), reinterpret_cast<const void*>(k_wf_trace_fallback<1, 1>),
-                reinterpret_cast<const void*>(k_wf_trace_fallback<2, 0>), reinterpret_cast<const void*>(k_wf_trace_fallback<2, 1>),
-                reinterpret_cast<const void*>(k_debug_intersect<0>), reinterpret_cast<const void*>(k_debug_intersect<2>),
-                reinterpret_cast<const void*>(k_debug_sample_radiance<0>), reinterpret_cast<const void*>(k_debug_sample_radiance<2>),
-                reinterpret_cast<const void*>(k_sampler_pass<0>), reinterpret_cast<const void*>(k_sampler_pass<2>), reinterpret_cast<const void*>(k_sampler_pass<3>),
-                reinterpret_cast<const void*>(k_sampler_pass<0, FEAT_NONE>), reinterpret_cast<const void*>(k_sampler_pass<2, FEAT_NONE>), reinterpret_cast<const void*>(k_sampler_pass<3, FEAT_NONE>),
-                reinterpret_cast<const void*>(k_debug_intersect<3>), reinterpret_cast<const void*>(k_debug_sample_radiance<3>)};
-            for (const void* k : traversing) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            (void)hipGetLastError();
-        }
-    }
+    else if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) { set_error("hipEventCreate failed"); return TRAY_E_DEVICE; }
+    return TRAY_OK;
+}
+
+// Past the default dynamic-LDS window of 32 KB: raises the per-kernel limit (160 KB LDS per CU) of every kernel that is launched with the scene's
+// stack_bytes (or its LDS part)
+static void raise_lds_limit(uint32_t stack_bytes) {
+    if (stack_bytes <= 32u * 1024u) return;
+    const void* const traversing[] = {
+        reinterpret_cast<const void*>(k_path_tiles<0, FEAT_NONE>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL>),
+        reinterpret_cast<const void*>(k_path_tiles<0, FEAT_SPEC>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL | FEAT_SPEC>),
+        reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL>),
+        reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX>),
+        reinterpret_cast<const void*>(k_path_tiles<1, FEAT_NONE>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL>),
+        reinterpret_cast<const void*>(k_path_tiles<1, FEAT_SPEC>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL | FEAT_SPEC>),
+        reinterpret_cast<const void*>(k_path_tiles<0, FEAT_NONE, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_MERL | FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_PATH, true>),
+        reinterpret_cast<const void*>(k_path_tiles<1, FEAT_NONE, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_MERL | FEAT_SPEC, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL, TRAY_INTEGRATOR_PATH, true>), reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_PATH, true>),
+        reinterpret_cast<const void*>(k_path_tiles<0, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>),
+        reinterpret_cast<const void*>(k_path_tiles<1, FEAT_ALL | FEAT_TEX, TRAY_INTEGRATOR_WHITTED>),
+        reinterpret_cast<const void*>(k_wf_trace_dyn<0, 0>), reinterpret_cast<const void*>(k_wf_trace_dyn<0, 1>),
+        reinterpret_cast<const void*>(k_wf_trace_dyn<1, 0>), reinterpret_cast<const void*>(k_wf_trace_dyn<1, 1>),
+        reinterpret_cast<const void*>(k_wf_trace_dyn<2, 0>), reinterpret_cast<const void*>(k_wf_trace_dyn<2, 1>),
+        reinterpret_cast<const void*>(k_wf_trace_fallback<0, 0>), reinterpret_cast<const void*>(k_wf_trace_fallback<0, 1>),
+        reinterpret_cast<const void*>(k_wf_trace_fallback<1, 0>), reinterpret_cast<const void*>(k_wf_trace_fallback<1, 1>),
+        reinterpret_cast<const void*>(k_wf_trace_fallback<2, 0>), reinterpret_cast<const void*>(k_wf_trace_fallback<2, 1>),
+        reinterpret_cast<const void*>(k_debug_intersect<0>), reinterpret_cast<const void*>(k_debug_intersect<2>),
+        reinterpret_cast<const void*>(k_debug_sample_radiance<0>), reinterpret_cast<const void*>(k_debug_sample_radiance<2>),
+        reinterpret_cast<const void*>(k_sampler_pass<0>), reinterpret_cast<const void*>(k_sampler_pass<2>), reinterpret_cast<const void*>(k_sampler_pass<3>),
+        reinterpret_cast<const void*>(k_sampler_pass<0, FEAT_NONE>), reinterpret_cast<const void*>(k_sampler_pass<2, FEAT_NONE>), reinterpret_cast<const void*>(k_sampler_pass<3, FEAT_NONE>),
+        reinterpret_cast<const void*>(k_debug_intersect<3>), reinterpret_cast<const void*>(k_debug_sample_radiance<3>)};
+    for (const void* k : traversing) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stack_bytes);
+    (void)hipGetLastError();
+}
+
+// workgroups of the persistent tile kernel: what fits the device, asked of the instantiation launch_tiles will run
+static void scene_occupancy(TrayDeviceScene* s) {
     int per_cu = 0, cus = 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, s->device) == hipSuccess) cus = prop.multiProcessorCount;
-    hipError_t occ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tile_kernel(s), TR_BLOCK, s->stack_bytes);   // of the instantiation launch_tiles will run
+    hipError_t occ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tile_kernel(s), TR_BLOCK, s->stack_bytes);
     if (occ != hipSuccess || per_cu < 1) per_cu = 1;
-    s->deferred_n_moving = 0;
-    for (uint32_t i = 0; i < f->n_instances; ++i) if (f->instances[i].animated) s->deferred_n_moving++;
-    {   // how many records per time index a later frame of this scene can need (xf_table_ensure sizes the table's buffer once)
-        auto movable = [&](uint32_t first, uint32_t count) {
-            for (uint32_t l = first; l < first + count && l < f->n_xf_levels; ++l) if (f->xf_levels[l].kf_count > 1u) return true;
-            return false;
-        };
-        s->xf_movable = movable(f->camera.xf_first, f->camera.xf_count) ? 1u : 0u;
-        for (uint32_t i = 0; i < f->n_instances; ++i) if (movable(f->instances[i].xf_first, f->instances[i].xf_count)) s->xf_movable++;
-    }
     if (cus < 1) cus = 256;
     s->n_blocks = cus * per_cu;
     if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] tile kernel: %d workgroups per CU (dynamic LDS %u B)\n", per_cu, s->stack_bytes);
-    if (s->deferred_n_moving > 64) {
-        tray_scene_destroy(s); set_error("more than 64 instances move within one frame: the per-path transform cache does not cover that"); return TRAY_E_UNSUPPORTED;
-    }
-    if (s->animated && s->deferred_n_moving > 0) {   // the moving instances of the per-path transform cache (dev_geom.h)
-        std::vector<uint32_t> ids(s->deferred_n_moving, 0u);
-        for (uint32_t i = 0; i < f->n_instances; ++i)
-            if (f->instances[i].animated && f->instances[i].moving_slot < ids.size()) ids[f->instances[i].moving_slot] = i;
-        const uint32_t* d_ids = nullptr;
-        if (upload(s, "moving_ids", false, ids.data(), ids.size(), &d_ids) != TRAY_OK) { tray_scene_destroy(s); return TRAY_E_NOMEM; }
-        s->dev.moving_ids = d_ids;
-        s->dev.n_moving = s->deferred_n_moving;
-        s->dev.xf_stride = s->deferred_n_moving;
-        s->dev.xf_aos = s->wavefront ? 1u : 0u;
-    }
+}
+
+// The launch buffers: the previous frame's in one move (freeing and allocating the 20 GB of a table costs 4 s -- profiles/r06_d_frame_overheads.txt --, a
+// pool seconds more), then lb_fit drops what this frame cannot use
+static int scene_launch_buffers(TrayDeviceScene* s) {
+    TrayDeviceScene* donor = s->donor;
     s->wf_req_slots = donor ? donor->wf_req_slots : 0u; s->wf_req_views = donor ? donor->wf_req_views : 0u; s->wf_req_slices = donor ? donor->wf_req_slices : 0u;
     s->xf_table_req = donor ? donor->xf_table_req : -1;
-    // the launch buffers: the previous frame's in one move (freeing and allocating the 20 GB of a table costs 4 s -- profiles/r06_d_frame_overheads.txt --, a
-    // pool seconds more), then lb_fit drops what this frame cannot use
     if (donor) s->lb = std::exchange(donor->lb, LaunchBuffers{});
     const uint32_t handed_slots = s->lb.wf.pool.n_slots, handed_table_use = s->lb.last_used_table;   // (TRAYHIP_STATS)
     const bool pool_kept = lb_fit(s);
@@ -841,9 +684,33 @@ static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDevic
                 pool_kept ? "kept" : "not kept", handed_slots ? 1 : 0, s->wavefront ? 1 : 0, donor->stack_bytes, s->stack_bytes, donor->quad_stack_words, s->quad_stack_words,
                 donor->animated ? 1 : 0, s->animated ? 1 : 0, handed_slots, s->lb.xf_cache_lanes, handed_table_use ? 1 : 0, s->lb.d_xf_table ? "kept" : "none");
     // the tile kernel's cache is allocated here, the wavefront schedule's by the first launch that evaluates per path (launch_prepare)
-    if (s->dev.n_moving && !s->wavefront && !s->lb.xf_cache && xf_cache_alloc(s, s->lb.xf_cache_lanes) != TRAY_OK) { tray_scene_destroy(s); return TRAY_E_NOMEM; }
+    if (s->dev.n_moving && !s->wavefront && !s->lb.xf_cache && xf_cache_alloc(s, s->lb.xf_cache_lanes) != TRAY_OK) return TRAY_E_NOMEM;
+    return TRAY_OK;
+}
+
+static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDeviceScene** out) {
+    if (!f || !out) { set_error("tray_scene_create: null argument"); return TRAY_E_INVALID; }
+    *out = nullptr;
+    if (const tr_plan::Refusal no = tr_plan::refuse(f, donor == nullptr); no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
+    std::unique_ptr<TrayDeviceScene, decltype(&tray_scene_destroy)> owner(new TrayDeviceScene(), tray_scene_destroy);   // (a step that fails destroys what was built)
+    TrayDeviceScene* s = owner.get();
+    s->identity = scene_identity(f);
+    s->device = donor ? donor->device : g_device;
+    s->donor = donor;
+    if (hipSetDevice(s->device) != hipSuccess) { set_error("hipSetDevice failed (is a GPU present?)"); return TRAY_E_DEVICE; }
+    SceneTrees trees;
+    tr_plan::ScenePlan plan;
+    std::vector<DevMaterial> mats(f->n_materials);
+    for (uint32_t i = 0; i < f->n_materials; ++i) mats[i] = lower_material(f->materials[i], f->merl_tables);
+    int rc = scene_trees(f, s, trees);
+    if (rc == TRAY_OK) rc = scene_plan(f, s, mats, plan);
+    if (rc == TRAY_OK) rc = scene_upload(f, s, trees, mats, plan);
+    if (rc != TRAY_OK) return rc;
+    raise_lds_limit(s->stack_bytes);
+    scene_occupancy(s);
+    if (scene_launch_buffers(s) != TRAY_OK) return TRAY_E_NOMEM;
     s->donor = nullptr;
-    *out = s;
+    *out = owner.release();
     return TRAY_OK;
 }
 
@@ -1098,8 +965,8 @@ int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t
 }
 
 static bool distinct_aligned(const void* const* bufs, size_t n);
-// the ANIM argument of the first-hit kernels: the set the debug kernels have (2: the spline stacks evaluated at every use, no transform cache)
-static int first_hit_anim(const TrayDeviceScene* s) { return s->deforming ? 3 : s->animated ? 2 : 0; }
+// the ANIM argument of the debug, sampler and first-hit kernels
+static int anim_debug(const TrayDeviceScene* s) { return tr_plan::anim_debug(s->deforming, s->animated); }
 
 int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint32_t sample_begin, uint32_t sample_end,
                                  uint64_t seed, float* albedo_dev, float* normal_dev, float* depth_dev, void* stream_) {
@@ -1115,7 +982,7 @@ int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32
     HIP_CHECK(hipSetDevice(s->device));
     if (tile_count == 0) return TRAY_OK;   // (an empty queue: nothing to add)
     // s->dev, not the launch copy: no per-path transform cache and no table, so the call needs none of a render's launch buffers
-    tr_firsthit::tiles(first_hit_anim(s), static_cast<hipStream_t>(stream_), s->stack_bytes, s->dev, s->d_tiles + tile_start, tile_count, spp,
+    tr_firsthit::tiles(anim_debug(s), static_cast<hipStream_t>(stream_), s->stack_bytes, s->dev, s->d_tiles + tile_start, tile_count, spp,
                        tr_rules::frame_key(seed, s->dev.frame), sample_begin, sample_end, albedo_dev, normal_dev, depth_dev);
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;
@@ -1531,7 +1398,7 @@ static int launch_sampler(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_
             tr_rules::sampler_round(sp, j, smp_end ? smp_end - smp_begin : 0u);
             const uint32_t group = tr_rules::sampler_group(sp.count, SP_GROUP_MAX);
             const dim3 grid((n_items + group - 1u) / group), block(TR_BLOCK);
-            const int anim = s->deforming ? 3 : s->animated ? 2 : 0;
+            const int anim = anim_debug(s);
             const bool lean = sampler_lean(s->feat, s->dev.integrator);
             if (sp.kind == TRAY_SAMPLER_LOW_DISCREPANCY && smp_end)
                 tr_ranges::sampler_pass(anim, lean, grid, block, s->stack_bytes, stream, s->dev, tiles, item0, n_items, chunk, chunk_stride, kf, sp, px_state, px_lum,
@@ -2116,8 +1983,9 @@ int tray_debug_intersect(TrayDeviceScene* s, uint32_t n, const TrayRay* rays, Tr
     if (e == hipSuccess) e = hipMemcpy(d_r, rays, n * sizeof(TrayRay), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         // ANIM = 2: debug grids are sized by the item count, not by the transform cache, so the spline stacks are evaluated at every use
-        if (s->deforming) hipLaunchKernelGGL(k_debug_intersect<3>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_r, d_h);
-        else if (s->animated) hipLaunchKernelGGL(k_debug_intersect<2>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_r, d_h);
+        const int anim = anim_debug(s);
+        if (anim == 3) hipLaunchKernelGGL(k_debug_intersect<3>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_r, d_h);
+        else if (anim == 2) hipLaunchKernelGGL(k_debug_intersect<2>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_r, d_h);
         else hipLaunchKernelGGL(k_debug_intersect<0>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_r, d_h);
         e = hipGetLastError();
     }
@@ -2148,9 +2016,10 @@ int tray_debug_sample_radiance(TrayDeviceScene* s, uint32_t n, const uint32_t* p
         uint32_t kf = mix((uint32_t)seed + 0x9E3779B9u);
         kf = mix(kf ^ (uint32_t)(seed >> 32));
         kf = mix(kf + s->dev.frame);
-        if (s->deforming)
+        const int anim = anim_debug(s);
+        if (anim == 3)
             hipLaunchKernelGGL(k_debug_sample_radiance<3>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_in, d_in + n, d_in + 2 * (size_t)n, spp, kf, d_out);
-        else if (s->animated)
+        else if (anim == 2)
             hipLaunchKernelGGL(k_debug_sample_radiance<2>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_in, d_in + n, d_in + 2 * (size_t)n, spp, kf, d_out);
         else
             hipLaunchKernelGGL(k_debug_sample_radiance<0>, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), s->stack_bytes, 0, s->dev, n, d_in, d_in + n, d_in + 2 * (size_t)n, spp, kf, d_out);
@@ -2178,7 +2047,7 @@ int tray_debug_first_hit(TrayDeviceScene* s, uint32_t n, const uint32_t* px, con
     if (e == hipSuccess) e = hipMemcpy(d_in + n, py, n * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_in + 2 * (size_t)n, si, n * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        tr_firsthit::debug(first_hit_anim(s), s->stack_bytes, s->dev, n, d_in, d_in + n, d_in + 2 * (size_t)n, spp, tr_rules::frame_key(seed, s->dev.frame), d_out);
+        tr_firsthit::debug(anim_debug(s), s->stack_bytes, s->dev, n, d_in, d_in + n, d_in + 2 * (size_t)n, spp, tr_rules::frame_key(seed, s->dev.frame), d_out);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, 12 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost);

@@ -540,6 +540,31 @@ int tray_denoise_demodulated_device(uint32_t width, uint32_t height, const float
                                     uint32_t radius, uint32_t patch, float k, uint32_t radius2, uint32_t patch2, float k2, float* out_dev,
                                     void* scratch_dev, void* stream);
 
+/* tray_denoise_temporal_device on albedo-demodulated films: every frame's colour is divided by that frame's own first-hit albedo, the smooth
+ * remainders are filtered together, and the centre frame's texture is multiplied back in. Where the texture itself changes from frame to frame
+ * (an animated image, a moving textured object) a neighbour's colour patches do not match the centre's, while the remainders do.
+ * - Frames as in tray_denoise_temporal_device; frame j (0 = the centre) also has an albedo film ALB_j: albedo_dev, nb_albedo_dev[j - 1].
+ * - Scale. s_j(p) from ALB_j by tray_denoise_demodulated_device's rule: max(ALB_c / ALB.w, 0) + TRAY_DEMOD_EPS where ALB.w > 0 and all four
+ *   words are finite, else 1.
+ * - Demodulated films. E'_j = (E_j.rgb / s_j, E_j.w), O'_j likewise. A pixel of frame j is valid by tray_denoise_device's rule applied to
+ *   E'_j and O'_j: both weights > 0 and all eight words of the QUOTIENTS finite.
+ * - Filter. D = tray_denoise_temporal_device(E'_0, O'_0, N, E'_1 ..., O'_1 ..., radius, radius_t, patch, k).
+ * - Output. out = (D.rgb * s_0, 1). f32, unfused, IEEE division. No atomics: the same bits in every run.
+ * - With N = 0 the output is tray_denoise_demodulated_device's with radius2 = 0, bit for bit; with albedo films without a valid pixel it is
+ *   tray_denoise_temporal_device's (x / 1 and x * 1 are exact); in general it is the output of the three steps above made one after the other.
+ * tray_denoise_temporal_demodulated_scratch_bytes: tray_denoise_temporal_scratch_bytes, 128 bytes per pixel whatever N is, laid out as there
+ * (0 if width or height is 0): E' and O' are never written to memory. nb_even_dev / nb_odd_dev / nb_albedo_dev are HOST arrays of
+ * n_neighbours device pointers, read during the call; they may be null only when n_neighbours is 0. 3 (N + 1) kernel launches on `stream`
+ * (per frame one that resolves the demodulated films, tray_denoise_device's second preparing one, and one pass over the 32 x 16 tiles, the last
+ * of which scales its output), asynchronous, no host synchronisation, on the current device (tray_init).
+ * Returns TRAY_E_INVALID, before any device call, under tray_denoise_temporal_device's rules, if an albedo film is null, or unless all
+ * 3 (N + 1) films, out_dev and scratch_dev are pairwise different buffers, 16-byte aligned. */
+uint64_t tray_denoise_temporal_demodulated_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_demodulated_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                             uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                             const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
+                                             float* out_dev, void* scratch_dev, void* stream);
+
 /* tray_render_noise_target_device with the stopping rule on the image that will be shown: the rounds, the even / odd split, n_t, the outputs,
  * TrayKernelTiming and the error returns are that call's, word for word, and the films it returns are still the unfiltered films of exactly
  * [0, n_t) of every tile. One thing differs: the error of a tile in a round is that call's metric evaluated on (fa, fb) =

@@ -416,6 +416,20 @@ class Hip:
             raise ValueError(f"{what}: even and odd must be two (h, w, 4) films of one size")
         return as_numpy, e, o
 
+    def _film_on_device(self, what, film):
+        """one (h, w, 4) film -- a numpy array or a torch tensor on this device -- as a contiguous float32 tensor: uploaded once, or as it is"""
+        import torch
+        dev = f"cuda:{self.device}"
+        if isinstance(film, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(film, dtype=np.float32)).to(dev)
+        else:
+            if film.device != torch.device(dev):
+                raise ValueError(f"{what}: the films must live on {dev}")
+            t = film.to(torch.float32).contiguous()
+        if t.dim() != 3 or t.shape[2] != 4:
+            raise ValueError(f"{what}: a film must be (h, w, 4)")
+        return t
+
     def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, passes=1,
                 radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2, albedo=None):
         """The dual-buffer NL-means filter of include/trayhip.h (tray_denoise_device) of two half films, e.g. the even and odd film of a
@@ -532,30 +546,41 @@ class Hip:
             rt.add_pixels(out.reshape(-1).cpu().numpy())
         return result
 
-    def _denoise_temporal_device(self, centre, neighbours, radius, radius_t, patch, k):
+    def _denoise_temporal_device(self, centre, neighbours, radius, radius_t, patch, k, albedos=None):
         """tray_denoise_temporal_device of (even, odd) pairs of (h, w, 4) float32 tensors of this device on the current stream: `centre` filtered
-        with `neighbours` (a list of pairs, in order); returns the output tensor"""
+        with `neighbours` (a list of pairs, in order); returns the output tensor. albedos: the albedo tensors of the centre and of the neighbours,
+        in that order (tray_denoise_temporal_demodulated_device)"""
         import torch
         e, o = centre
         h, w = int(e.shape[0]), int(e.shape[1])
         n = len(neighbours)
-        pointers = lambda i: (C.c_void_p * max(n, 1))(*[pair[i].data_ptr() for pair in neighbours])
+        array = lambda tensors: (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tensors])
+        pointers = lambda i: array([pair[i] for pair in neighbours])
         with torch.cuda.device(self.device):
             out = torch.empty_like(e)
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            nbytes = lib().tray_denoise_temporal_scratch_bytes if albedos is None else lib().tray_denoise_temporal_demodulated_scratch_bytes
+            scratch = torch.empty(max(int(nbytes(w, h)), 16), dtype=torch.uint8, device=e.device)
             stream = torch.cuda.current_stream().cuda_stream
             check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), n, pointers(0), pointers(1), int(radius),
-                                                     int(radius_t), int(patch), float(k), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                                                     C.c_void_p(stream) if stream else None))
+            tail = (int(radius), int(radius_t), int(patch), float(k), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                    C.c_void_p(stream) if stream else None)
+            if albedos is None:
+                check(lib().tray_denoise_temporal_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), n, pointers(0), pointers(1), *tail))
+            else:
+                check(lib().tray_denoise_temporal_demodulated_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()),
+                                                                     C.c_void_p(albedos[0].data_ptr()), n, pointers(0), pointers(1), array(albedos[1:]),
+                                                                     *tail))
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out
 
     def denoise_temporal(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
-                         k=_lib.TRAY_DENOISE_K):
+                         k=_lib.TRAY_DENOISE_K, albedos=None):
         """denoise() for a frame of a sequence (tray_denoise_temporal_device): `frames` is a list of (even, odd) half-film pairs of consecutive frames,
         as denoise() takes them; frames[centre] is filtered, and its filter also searches a window of radius_t in each of the other frames, in
-        list order (at most 8 of them). Returns the same kind it was given. A one-element list gives denoise()'s image to the bit."""
+        list order (at most 8 of them). Returns the same kind it was given. A one-element list gives denoise()'s image to the bit.
+        albedos: a list of first-hit albedo films (render_first_hit), one per frame, of the frames' kind and size: every frame's colour is divided
+        by its own albedo, the remainders are filtered together and frames[centre]'s texture is multiplied back in
+        (tray_denoise_temporal_demodulated_device); a one-element list then gives denoise(albedo=...)'s image to the bit."""
         frames = list(frames)
         if not 0 <= int(centre) < len(frames):
             raise ValueError("denoise_temporal: centre must index frames")
@@ -565,16 +590,30 @@ class Hip:
         pairs = [(e, o) for _, e, o in on_device]
         if any(e.shape != pairs[0][0].shape for e, _ in pairs):
             raise ValueError("denoise_temporal: the frames must be of one size")
-        out = self._denoise_temporal_device(pairs[int(centre)], pairs[:int(centre)] + pairs[int(centre) + 1:], radius, radius_t, patch, k)
+        c = int(centre)
+        if albedos is None:
+            out = self._denoise_temporal_device(pairs[c], pairs[:c] + pairs[c + 1:], radius, radius_t, patch, k)
+        else:
+            albedos = list(albedos)
+            if len(albedos) != len(frames):
+                raise ValueError("denoise_temporal: albedos must hold one albedo film per frame")
+            if any(isinstance(a, np.ndarray) != on_device[0][0] for a in albedos):
+                raise TypeError("denoise_temporal: the frames and the albedo films must all be numpy arrays or all be torch tensors")
+            alb = [self._film_on_device("denoise_temporal", a) for a in albedos]
+            if any(a.shape != pairs[0][0].shape for a in alb):
+                raise ValueError("denoise_temporal: the albedo films must have the frames' size")
+            out = self._denoise_temporal_device(pairs[c], pairs[:c] + pairs[c + 1:], radius, radius_t, patch, k, [alb[c]] + alb[:c] + alb[c + 1:])
         return out.cpu().numpy() if on_device[0][0] else out
 
     def render_sequence_denoised(self, scene, config, frames, reach=1, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
-                                 patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+                                 patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, demodulate=False, feature_spp=None):
         """Generator over the consecutive frame numbers `frames`: config.select_blocks of every frame rendered once as its two half films (the sample
         ranges [0, spp / 2) and [spp / 2, spp) of the round_spp(config.spp)-sample frame, as render_denoised without a threshold) and filtered
         with the up to `reach` frames before and after it that belong to `frames` (denoise_temporal, the neighbours in ascending frame order);
         yields (frame, rgbw) with rgbw an (h, w, 4) numpy array of weight 1. At most 2 reach + 1 film pairs live on the device. One seed, self.seed:
-        the frame number already keys the sampler. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        the frame number already keys the sampler. demodulate=True also renders every frame's first-hit albedo film once, from the samples
+        [0, feature_spp or spp) of that frame, and filters with denoise_temporal(albedos=...): at most 2 reach + 1 albedo films live on the device
+        beside one throw-away normal and depth film. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
         import torch
         frames, reach = [int(f) for f in frames], int(reach)
         if any(b != a + 1 for a, b in zip(frames, frames[1:])):
@@ -586,21 +625,34 @@ class Hip:
         spp = self._select_sampler(scene.device_scene(frames[0], self.device), config.spp)
         if spp < 2:
             raise ValueError("render_sequence_denoised: two half films need spp >= 2")
+        n_feat = spp if feature_spp is None else int(feature_spp)
+        if demodulate and not 1 <= n_feat <= spp:
+            raise ValueError(f"render_sequence_denoised: feature_spp must lie in [1, {spp}]")
         film = scene.flatten(frames[0]).contents.film
         w, h = int(film.width), int(film.height)
-        held, spare = {}, []   # frame -> its (even, odd) on the device; pairs of frames that are done, to be rendered into again
+        n_films = 3 if demodulate else 2
+        held, spare = {}, []   # frame -> its (even, odd[, albedo]) on the device; the films of frames that are done, to be rendered into again
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
+            new_film = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+            throw_away = (new_film(), new_film()) if demodulate else None   # the normal and depth films nobody reads
             for f in frames:
                 window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
                 for g in window:
                     if g not in held:
-                        pair = spare.pop() if spare else tuple(torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}") for _ in range(2))
-                        for half, rng in zip(pair, ((0, spp // 2), (spp // 2, spp))):
+                        films = spare.pop() if spare else tuple(new_film() for _ in range(n_films))
+                        for half, rng in zip(films, ((0, spp // 2), (spp // 2, spp))):
                             half.zero_()
                             self.render_samples_device(scene, g, config.select_blocks, spp, rng, half.data_ptr(), stream or None)
-                        held[g] = pair
-                out = self._denoise_temporal_device(held[f], [held[g] for g in window if g != f], radius, radius_t, patch, k)
+                        if demodulate:
+                            for t in (films[2],) + throw_away:
+                                t.zero_()
+                            self.render_first_hit_device(scene, g, config.select_blocks, spp, (0, n_feat), films[2].data_ptr(),
+                                                         throw_away[0].data_ptr(), throw_away[1].data_ptr(), stream or None)
+                        held[g] = films
+                others = [g for g in window if g != f]
+                out = self._denoise_temporal_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k,
+                                                    *(([held[g][2] for g in [f] + others],) if demodulate else ()))
                 for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
                     spare.append(held.pop(g))
                 yield f, out.cpu().numpy()

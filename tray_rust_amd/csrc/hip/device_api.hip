@@ -15,6 +15,7 @@
 #include "temporal.h"
 #include "guided.h"
 #include "first_hit.h"
+#include "tdemod.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 #include "scene_plan.h"
@@ -1355,6 +1356,46 @@ int tray_denoise_demodulated_device(uint32_t width, uint32_t height, const float
     if (radius2) two_pass_launches(stream, width, height, e, o, radius, patch, k, radius2, patch2, k2, out_dev, scratch_dev);
     else tr_denoise::denoise(stream, e, o, width, height, radius, patch, k, out_dev, scratch_dev);
     tr_firsthit::remodulate(stream, albedo_dev, width, height, out_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_demodulated_scratch_bytes(uint32_t width, uint32_t height) { return tr_tdemod::scratch_bytes(width, height); }
+
+int tray_denoise_temporal_demodulated_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                             uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                             const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k, float* out_dev,
+                                             void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_temporal_demodulated_device");
+    if (!even_dev || !odd_dev || !albedo_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    if (radius_t < 1u || radius_t > radius) { set_error(who + ": 1 <= radius_t <= radius is required"); return TRAY_E_INVALID; }
+    if (n_neighbours > TRAY_DENOISE_MAX_NEIGHBOURS) {
+        set_error(who + ": at most " + std::to_string(TRAY_DENOISE_MAX_NEIGHBOURS) + " neighbouring frames"); return TRAY_E_INVALID;
+    }
+    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev || !nb_albedo_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const void* bufs[3u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 2u] = {even_dev, odd_dev, albedo_dev, out_dev, scratch_dev};
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        if (!nb_even_dev[j] || !nb_odd_dev[j] || !nb_albedo_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
+        bufs[5u + 3u * j] = nb_even_dev[j];
+        bufs[6u + 3u * j] = nb_odd_dev[j];
+        bufs[7u + 3u * j] = nb_albedo_dev[j];
+    }
+    if (!distinct_aligned(bufs, 5u + 3u * n_neighbours)) {
+        set_error(who + ": every frame's two films and albedo film, the output and the scratch buffer must be different buffers, 16-byte aligned");
+        return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_tdemod::Layout l = tr_tdemod::layout(scratch_dev, width, height);
+    // as tray_denoise_temporal_device: per frame two preparing launches and one pass; the centre's albedo scales the last pass's output
+    tr_tdemod::prepare(stream, even_dev, odd_dev, albedo_dev, width, height, l.centre);
+    tr_tdemod::pass(stream, l.centre, l.centre, albedo_dev, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, out_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_tdemod::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
+        tr_tdemod::pass(stream, l.centre, l.neighbour, albedo_dev, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
+    }
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;
 }

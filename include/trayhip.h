@@ -565,6 +565,80 @@ int tray_denoise_temporal_demodulated_device(uint32_t width, uint32_t height, co
                                              const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
                                              float* out_dev, void* scratch_dev, void* stream);
 
+/* Two-pass temporal NL-means: a second pass over ALL frames whose weights are measured on first-pass output. Three calls; the third is defined
+ * by the first two and by tray_denoise_halves_device.
+ *
+ * tray_denoise_temporal_halves_device: the two cross-filtered halves of tray_denoise_temporal_device's statement as RGBW films, in
+ * tray_denoise_halves_device's convention: fa = (A(p), wA), fb = (B(p), wB) with A, B the quotients of that statement over all frames' windows,
+ * wA = 1 if A's denominator sum_j sum_q w_b(p, q, j) is > 0, else 0 (then A = 0), wB likewise. The arguments are tray_denoise_temporal_device's
+ * with fa_dev, fb_dev in place of out_dev. (fa.rgb + fb.rgb) * 0.5f is tray_denoise_temporal_device's out.rgb, bit for bit; with N = 0 the
+ * films are tray_denoise_halves_device's with blocks_dev = null, bit for bit. No atomics: the same bits in every run.
+ * tray_denoise_temporal_halves_scratch_bytes: 128 bytes per pixel whatever N is, laid out as tray_denoise_temporal_device's (the centre's
+ * records, 48; the current neighbour's, 48; the sums between passes, 32; 0 if width or height is 0). 3 (N + 1) kernel launches on `stream`:
+ * per frame, the centre first, tray_denoise_device's two preparing ones and one pass over the 32 x 16 tiles, the last of which stores the halves.
+ *
+ * tray_denoise_temporal_guided_device: tray_denoise_temporal_device with the weights measured on guides, as tray_denoise_guided_device measures
+ * them. Frame j (0 = the centre; frames 1 ... N in the caller's order) has values (E_j, O_j) = (even_dev, odd_dev) / (nb_even_dev[j - 1],
+ * nb_odd_dev[j - 1]) and a guide (GA_j, GB_j) = (guide_a_dev, guide_b_dev) / (nb_guide_a_dev[j - 1], nb_guide_b_dev[j - 1]).
+ * - Values. a_j, b_j and valid_j are resolved from (E_j, O_j) as tray_denoise_device resolves them.
+ * - Guides. ga_j, gb_j, gvalid_j and Vg_j are resolved from (GA_j, GB_j), each frame on its own, as tray_denoise_guided_device resolves its guide.
+ * - Window and order. As tray_denoise_temporal_device: q runs over p + [-radius, radius]^2 in frame 0 and over p + [-radius_t, radius_t]^2 in
+ *   every frame j >= 1; the sums run over frame 0 first, then frames 1 ... N in the given order; within a frame dy outer and dx inner, ascending.
+ * - Distance of p (frame 0) and q (frame j) in guide buffer x (ga or gb): t(p', q') as in tray_denoise_device from x_0(p'), Vg_0(p'), x_j(q'),
+ *   Vg_j(q'); pair(n) = gvalid_0(p') gvalid_j(q') (0 outside the image); d2_x(p, q, j) = sum_n t(p', q') pair(n) / (3 sum_n pair(n)) over the
+ *   (2 patch + 1)^2 offsets n, p' = p + n, q' = q + n.
+ * - Weight. w_x(p, q, j) = exp(-max(0, d2_x)) if q is inside the image, valid_j(q) holds (the VALUES' validity) and sum_n pair(n) > 0, else 0.
+ * - Output. A(p) = sum_j sum_q w_gb(p, q, j) a_j(q) / sum_j sum_q w_gb(p, q, j), B(p) likewise with w_ga and b_j; a quotient whose denominator
+ *   is 0 is 0. out(p) = ((A + B) / 2, 1).
+ * - Arithmetic. f32, unfused, IEEE division, the library's own expf. No atomics: the same bits in every run.
+ * - Identities, to the bit: (i) with every frame's guide equal to its values (guide_a_dev == even_dev, guide_b_dev == odd_dev,
+ *   nb_guide_a_dev[j] == nb_even_dev[j], nb_guide_b_dev[j] == nb_odd_dev[j]; the guides may alias the films for that) the output is
+ *   tray_denoise_temporal_device's; (ii) with N = 0 it is tray_denoise_guided_device's.
+ * - Every output channel lies between the minimum and the maximum of that channel of a_j and b_j over the valid pixels of the pixel's windows
+ *   in all frames, up to rounding: the guides only choose weights.
+ * tray_denoise_temporal_guided_scratch_bytes: 176 bytes per pixel whatever N is (0 if width or height is 0), laid out as: the records of the
+ * centre's guide, 48 bytes per pixel; the records of the current neighbour's guide, 48; the records of the current frame's values, 48; the sums
+ * between passes, 32. 5 (N + 1) kernel launches on `stream`: per frame, the centre first, the two preparing ones for the frame's values, the
+ * same two for its guide, one pass over the 32 x 16 tiles.
+ *
+ * tray_denoise_temporal_two_pass_device: by definition
+ *   (fa_0, fb_0) = tray_denoise_temporal_halves_device(all frames, radius, radius_t, patch, k),
+ *   (fa_j, fb_j) = tray_denoise_halves_device(E_j, O_j, radius, patch, k, blocks_dev = null) for every neighbour j = 1 ... N,
+ *   out = tray_denoise_temporal_guided_device(values: the frames, guides: (fa_j, fb_j), radius2, radius_t2, patch2, k2):
+ * the centre is guided by its pilot over all frames, every neighbour by its own single-frame pilot. The output is what those calls give, bit
+ * for bit; with N = 0 it is tray_denoise_two_pass_device's, bit for bit.
+ * tray_denoise_temporal_two_pass_scratch_bytes: 256 bytes per pixel whatever N is (0 if width or height is 0), laid out as: the centre's
+ * records, 48 bytes per pixel (the first pass's, read again as the second pass's values of frame 0); the current neighbour's records, 48; the
+ * sums between passes, 32 (the first pass's, then the second's); fa and fb of the frame in hand, 16 each; the records of the centre's pilot,
+ * 48; the records of the current neighbour's pilot, 48. The neighbours are processed one at a time, so a neighbour's films are resolved once
+ * in each pass. 9 N + 6 kernel launches on `stream`, in this order: the 3 (N + 1) of tray_denoise_temporal_halves_device; the two preparing
+ * ones for (fa_0, fb_0) and the centre's guided pass; then per neighbour, in the caller's order, the two preparing ones for its films, its
+ * first-pass filter (the halves) over the 32 x 16 tiles, the two preparing ones for (fa_j, fb_j), its guided pass.
+ *
+ * All three: nb_* are HOST arrays of n_neighbours device pointers, read during the call; they may be null only when n_neighbours is 0. Every
+ * launch runs on `stream`, asynchronous, no host synchronisation, on the current device (tray_init).
+ * Return TRAY_E_INVALID, before any device call, under tray_denoise_temporal_device's rules for width, height, (radius, radius_t, patch, k)
+ * and n_neighbours; the two-pass call likewise for (radius2, radius_t2, patch2, k2): 1 <= radius_t2 <= radius2 <= 10, patch2 <= 3, k2 > 0 and
+ * finite; if a film, an output or scratch_dev is null; unless every buffer is 16-byte aligned; unless the outputs and scratch_dev differ from
+ * every film and from each other; if the two films of a pair (a frame's values, a frame's guide) are one buffer. In the halves and the
+ * two-pass call all 2 (N + 1) films are pairwise different, as in tray_denoise_temporal_device; in the guided call the films are only read and
+ * a guide may be its own frame's values. */
+#define TRAY_DENOISE_RADIUS_T2 3
+uint64_t tray_denoise_temporal_halves_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                        const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t,
+                                        uint32_t patch, float k, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream);
+uint64_t tray_denoise_temporal_guided_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* guide_a_dev,
+                                        const float* guide_b_dev, uint32_t n_neighbours, const float* const* nb_even_dev,
+                                        const float* const* nb_odd_dev, const float* const* nb_guide_a_dev, const float* const* nb_guide_b_dev,
+                                        uint32_t radius, uint32_t radius_t, uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream);
+uint64_t tray_denoise_temporal_two_pass_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                          const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t,
+                                          uint32_t patch, float k, uint32_t radius2, uint32_t radius_t2, uint32_t patch2, float k2, float* out_dev,
+                                          void* scratch_dev, void* stream);
+
 /* tray_render_noise_target_device with the stopping rule on the image that will be shown: the rounds, the even / odd split, n_t, the outputs,
  * TrayKernelTiming and the error returns are that call's, word for word, and the films it returns are still the unfiltered films of exactly
  * [0, n_t) of every tile. One thing differs: the error of a tile in a round is that call's metric evaluated on (fa, fb) =

@@ -473,15 +473,11 @@ class Hip:
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out.cpu().numpy() if as_numpy else out
 
-    def denoise_halves(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
-        """The two cross-filtered halves (A, B) of denoise()'s filter (tray_denoise_halves_device), films in and out as there: (A.rgb + B.rgb) / 2
-        is denoise()'s image to the bit, a half's weight is 1 where it exists and 0 where no neighbour had weight, and |A - B| / 2 is a per-pixel
-        confidence map of the denoised frame."""
+    def _denoise_halves_device(self, e, o, radius, patch, k, fa, fb):
+        """tray_denoise_halves_device over every block of two tensors of this device on the current stream, into the tensors fa and fb"""
         import torch
-        as_numpy, e, o = self._films_on_device("denoise_halves", even, odd)
         h, w = int(e.shape[0]), int(e.shape[1])
         with torch.cuda.device(self.device):
-            fa, fb = torch.empty_like(e), torch.empty_like(e)
             scratch = torch.empty(max(int(lib().tray_denoise_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
             stream = torch.cuda.current_stream().cuda_stream
             check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
@@ -489,6 +485,15 @@ class Hip:
                                                    C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()), C.c_void_p(scratch.data_ptr()),
                                                    C.c_void_p(stream) if stream else None))
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+
+    def denoise_halves(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+        """The two cross-filtered halves (A, B) of denoise()'s filter (tray_denoise_halves_device), films in and out as there: (A.rgb + B.rgb) / 2
+        is denoise()'s image to the bit, a half's weight is 1 where it exists and 0 where no neighbour had weight, and |A - B| / 2 is a per-pixel
+        confidence map of the denoised frame."""
+        import torch
+        as_numpy, e, o = self._films_on_device("denoise_halves", even, odd)
+        fa, fb = torch.empty_like(e), torch.empty_like(e)
+        self._denoise_halves_device(e, o, radius, patch, k, fa, fb)
         return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
 
     def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
@@ -573,48 +578,161 @@ class Hip:
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out
 
+    def _temporal_arrays(self, lists):
+        """host arrays of device pointers, one per list of tensors (never of length 0)"""
+        return [(C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts]) for ts in lists]
+
+    def _denoise_temporal_halves_device(self, centre, neighbours, radius, radius_t, patch, k, into=None):
+        """tray_denoise_temporal_halves_device of (even, odd) pairs of tensors of this device on the current stream; returns (fa, fb), written into
+        `into` if given"""
+        import torch
+        e, o = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        nbe, nbo = self._temporal_arrays([[p[0] for p in neighbours], [p[1] for p in neighbours]])
+        with torch.cuda.device(self.device):
+            fa, fb = into if into is not None else (torch.empty_like(e), torch.empty_like(e))
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_halves_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_halves_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), len(neighbours), nbe, nbo, int(radius),
+                                                            int(radius_t), int(patch), float(k), C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()),
+                                                            C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return fa, fb
+
+    def _denoise_temporal_guided_device(self, centre, neighbours, radius, radius_t, patch, k):
+        """tray_denoise_temporal_guided_device of (even, odd, guide_a, guide_b) tuples of tensors of this device on the current stream; returns the
+        output tensor"""
+        import torch
+        e, o, ga, gb = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(4)])
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_guided_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_guided_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(ga.data_ptr()),
+                                                            C.c_void_p(gb.data_ptr()), len(neighbours), *arrays, int(radius), int(radius_t), int(patch),
+                                                            float(k), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                                            C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return out
+
+    def _denoise_temporal_two_pass_device(self, centre, neighbours, radius, radius_t, patch, k, second):
+        """tray_denoise_temporal_two_pass_device of (even, odd) pairs of tensors of this device on the current stream; second: (radius2, radius_t2,
+        patch2, k2); returns the output tensor"""
+        import torch
+        e, o = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        nbe, nbo = self._temporal_arrays([[p[0] for p in neighbours], [p[1] for p in neighbours]])
+        radius2, radius_t2, patch2, k2 = second
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_two_pass_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_two_pass_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), len(neighbours), nbe, nbo, int(radius),
+                                                              int(radius_t), int(patch), float(k), int(radius2), int(radius_t2), int(patch2), float(k2),
+                                                              C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                                              C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return out
+
+    def _frames_on_device(self, what, frames, centre):
+        """(as_numpy, pairs with frames[centre] first): a list of (even, odd) pairs of one kind and size as tensors of this device"""
+        frames = list(frames)
+        if not 0 <= int(centre) < len(frames):
+            raise ValueError(f"{what}: centre must index frames")
+        on_device = [self._films_on_device(what, even, odd) for even, odd in frames]
+        if len({kind for kind, _, _ in on_device}) != 1:
+            raise TypeError(f"{what}: the frames must all be numpy arrays or all be torch tensors")
+        pairs = [(e, o) for _, e, o in on_device]
+        if any(e.shape != pairs[0][0].shape for e, _ in pairs):
+            raise ValueError(f"{what}: the frames must be of one size")
+        c = int(centre)
+        return on_device[0][0], [pairs[c]] + pairs[:c] + pairs[c + 1:]
+
+    def denoise_temporal_halves(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
+                                k=_lib.TRAY_DENOISE_K):
+        """The two cross-filtered halves (A, B) of denoise_temporal()'s filter (tray_denoise_temporal_halves_device), frames in as there and two
+        films out as from denoise_halves(): (A.rgb + B.rgb) / 2 is denoise_temporal()'s image to the bit, and a one-element list gives
+        denoise_halves()'s films to the bit."""
+        as_numpy, pairs = self._frames_on_device("denoise_temporal_halves", frames, centre)
+        fa, fb = self._denoise_temporal_halves_device(pairs[0], pairs[1:], radius, radius_t, patch, k)
+        return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
+
+    def denoise_temporal_guided(self, frames, guides, centre, radius=_lib.TRAY_DENOISE_RADIUS2, radius_t=_lib.TRAY_DENOISE_RADIUS_T2,
+                                patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
+        """denoise_temporal() with the weights measured on guides (tray_denoise_temporal_guided_device): `guides` holds one (guide_a, guide_b) pair
+        per frame, e.g. denoise_temporal_halves() of the centre and denoise_halves() of every other frame; the patch distances come from them, the
+        averaged colours from `frames`. All films of one kind and size. With the frames as their own guides the image is denoise_temporal()'s to
+        the bit; a one-element list gives denoise_guided()'s."""
+        frames, guides = list(frames), list(guides)
+        if len(guides) != len(frames):
+            raise ValueError("denoise_temporal_guided: guides must hold one pair of films per frame")
+        as_numpy, pairs = self._frames_on_device("denoise_temporal_guided", frames, centre)
+        guide_numpy, gpairs = self._frames_on_device("denoise_temporal_guided", guides, centre)
+        if guide_numpy != as_numpy:
+            raise TypeError("denoise_temporal_guided: the frames and the guides must all be numpy arrays or all be torch tensors")
+        if gpairs[0][0].shape != pairs[0][0].shape:
+            raise ValueError("denoise_temporal_guided: the guides must have the frames' size")
+        both = [fr + g for fr, g in zip(pairs, gpairs)]
+        out = self._denoise_temporal_guided_device(both[0], both[1:], radius, radius_t, patch, k)
+        return out.cpu().numpy() if as_numpy else out
+
     def denoise_temporal(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
-                         k=_lib.TRAY_DENOISE_K, albedos=None):
+                         k=_lib.TRAY_DENOISE_K, albedos=None, passes=1, radius2=_lib.TRAY_DENOISE_RADIUS2, radius_t2=_lib.TRAY_DENOISE_RADIUS_T2,
+                         patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2):
         """denoise() for a frame of a sequence (tray_denoise_temporal_device): `frames` is a list of (even, odd) half-film pairs of consecutive frames,
         as denoise() takes them; frames[centre] is filtered, and its filter also searches a window of radius_t in each of the other frames, in
         list order (at most 8 of them). Returns the same kind it was given. A one-element list gives denoise()'s image to the bit.
         albedos: a list of first-hit albedo films (render_first_hit), one per frame, of the frames' kind and size: every frame's colour is divided
         by its own albedo, the remainders are filtered together and frames[centre]'s texture is multiplied back in
-        (tray_denoise_temporal_demodulated_device); a one-element list then gives denoise(albedo=...)'s image to the bit."""
+        (tray_denoise_temporal_demodulated_device); a one-element list then gives denoise(albedo=...)'s image to the bit.
+        passes=2 (tray_denoise_temporal_two_pass_device): a second pass of (radius2, radius_t2, patch2, k2) over all frames takes its weights from
+        first-pass output -- frames[centre]'s from denoise_temporal_halves(), every other frame's from its own denoise_halves() -- and averages
+        the films again; a one-element list then gives denoise(passes=2)'s image to the bit. It does not combine with albedos."""
+        second = self._second_pass("denoise_temporal", passes, radius2, patch2, k2)
+        if second is not None and albedos is not None:
+            raise ValueError("denoise_temporal: passes=2 filters the films as they are; use albedos=None with it")
         frames = list(frames)
-        if not 0 <= int(centre) < len(frames):
-            raise ValueError("denoise_temporal: centre must index frames")
-        on_device = [self._films_on_device("denoise_temporal", even, odd) for even, odd in frames]
-        if len({kind for kind, _, _ in on_device}) != 1:
-            raise TypeError("denoise_temporal: the frames must all be numpy arrays or all be torch tensors")
-        pairs = [(e, o) for _, e, o in on_device]
-        if any(e.shape != pairs[0][0].shape for e, _ in pairs):
-            raise ValueError("denoise_temporal: the frames must be of one size")
+        as_numpy, pairs = self._frames_on_device("denoise_temporal", frames, centre)
         c = int(centre)
-        if albedos is None:
-            out = self._denoise_temporal_device(pairs[c], pairs[:c] + pairs[c + 1:], radius, radius_t, patch, k)
+        if second is not None:
+            out = self._denoise_temporal_two_pass_device(pairs[0], pairs[1:], radius, radius_t, patch, k, (radius2, radius_t2, patch2, k2))
+        elif albedos is None:
+            out = self._denoise_temporal_device(pairs[0], pairs[1:], radius, radius_t, patch, k)
         else:
             albedos = list(albedos)
             if len(albedos) != len(frames):
                 raise ValueError("denoise_temporal: albedos must hold one albedo film per frame")
-            if any(isinstance(a, np.ndarray) != on_device[0][0] for a in albedos):
+            if any(isinstance(a, np.ndarray) != as_numpy for a in albedos):
                 raise TypeError("denoise_temporal: the frames and the albedo films must all be numpy arrays or all be torch tensors")
             alb = [self._film_on_device("denoise_temporal", a) for a in albedos]
             if any(a.shape != pairs[0][0].shape for a in alb):
                 raise ValueError("denoise_temporal: the albedo films must have the frames' size")
-            out = self._denoise_temporal_device(pairs[c], pairs[:c] + pairs[c + 1:], radius, radius_t, patch, k, [alb[c]] + alb[:c] + alb[c + 1:])
-        return out.cpu().numpy() if on_device[0][0] else out
+            out = self._denoise_temporal_device(pairs[0], pairs[1:], radius, radius_t, patch, k, [alb[c]] + alb[:c] + alb[c + 1:])
+        return out.cpu().numpy() if as_numpy else out
 
     def render_sequence_denoised(self, scene, config, frames, reach=1, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
-                                 patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, demodulate=False, feature_spp=None):
+                                 patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, demodulate=False, feature_spp=None, passes=1,
+                                 radius2=_lib.TRAY_DENOISE_RADIUS2, radius_t2=_lib.TRAY_DENOISE_RADIUS_T2, patch2=_lib.TRAY_DENOISE_PATCH2,
+                                 k2=_lib.TRAY_DENOISE_K2):
         """Generator over the consecutive frame numbers `frames`: config.select_blocks of every frame rendered once as its two half films (the sample
         ranges [0, spp / 2) and [spp / 2, spp) of the round_spp(config.spp)-sample frame, as render_denoised without a threshold) and filtered
         with the up to `reach` frames before and after it that belong to `frames` (denoise_temporal, the neighbours in ascending frame order);
         yields (frame, rgbw) with rgbw an (h, w, 4) numpy array of weight 1. At most 2 reach + 1 film pairs live on the device. One seed, self.seed:
         the frame number already keys the sampler. demodulate=True also renders every frame's first-hit albedo film once, from the samples
         [0, feature_spp or spp) of that frame, and filters with denoise_temporal(albedos=...): at most 2 reach + 1 albedo films live on the device
-        beside one throw-away normal and depth film. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        beside one throw-away normal and depth film. passes=2 filters every frame as denoise_temporal(passes=2) filters the films rendered here,
+        to the bit: every frame's own first-pass halves (denoise_halves) are computed once, when it is rendered, and kept with its films (at most
+        2 reach + 1 such pairs and one pair for the centre's halves over all frames); it does not combine with demodulate.
+        LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
         import torch
+        second = self._second_pass("render_sequence_denoised", passes, radius2, patch2, k2)
+        if second is not None and demodulate:
+            raise ValueError("render_sequence_denoised: passes=2 filters the films as they are; use demodulate=False with it")
         frames, reach = [int(f) for f in frames], int(reach)
         if any(b != a + 1 for a, b in zip(frames, frames[1:])):
             raise ValueError("render_sequence_denoised: frames must be consecutive frame numbers")
@@ -630,12 +748,13 @@ class Hip:
             raise ValueError(f"render_sequence_denoised: feature_spp must lie in [1, {spp}]")
         film = scene.flatten(frames[0]).contents.film
         w, h = int(film.width), int(film.height)
-        n_films = 3 if demodulate else 2
-        held, spare = {}, []   # frame -> its (even, odd[, albedo]) on the device; the films of frames that are done, to be rendered into again
+        n_films = 3 if demodulate else 4 if second is not None else 2
+        held, spare = {}, []   # frame -> its (even, odd[, albedo | fa, fb]) on the device; the films of frames that are done, to be rendered into again
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream().cuda_stream
             new_film = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
             throw_away = (new_film(), new_film()) if demodulate else None   # the normal and depth films nobody reads
+            pilot = (new_film(), new_film()) if second is not None else None   # the halves of the frame in hand over all its frames
             for f in frames:
                 window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
                 for g in window:
@@ -649,10 +768,16 @@ class Hip:
                                 t.zero_()
                             self.render_first_hit_device(scene, g, config.select_blocks, spp, (0, n_feat), films[2].data_ptr(),
                                                          throw_away[0].data_ptr(), throw_away[1].data_ptr(), stream or None)
+                        if second is not None:   # the frame's own first-pass halves, once: the guide it brings to its neighbours' second passes
+                            self._denoise_halves_device(films[0], films[1], radius, patch, k, films[2], films[3])
                         held[g] = films
                 others = [g for g in window if g != f]
-                out = self._denoise_temporal_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k,
-                                                    *(([held[g][2] for g in [f] + others],) if demodulate else ()))
+                if second is not None:
+                    self._denoise_temporal_halves_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k, pilot)
+                    out = self._denoise_temporal_guided_device(held[f][:2] + pilot, [held[g] for g in others], radius2, radius_t2, patch2, k2)
+                else:
+                    out = self._denoise_temporal_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k,
+                                                        *(([held[g][2] for g in [f] + others],) if demodulate else ()))
                 for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
                     spare.append(held.pop(g))
                 yield f, out.cpu().numpy()

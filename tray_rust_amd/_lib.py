@@ -16,6 +16,7 @@ TRAY_PARTITION_TILES, TRAY_PARTITION_SAMPLES = 0, 1
 TRAY_DENOISE_RADIUS, TRAY_DENOISE_PATCH, TRAY_DENOISE_K = 7, 3, 0.45   # tray_denoise_device's defaults
 TRAY_DENOISE_RADIUS_T, TRAY_DENOISE_MAX_NEIGHBOURS = 3, 8   # tray_denoise_temporal_device's
 TRAY_DENOISE_RADIUS2, TRAY_DENOISE_PATCH2, TRAY_DENOISE_K2 = 5, 1, 1.0   # the second pass's defaults of tray_denoise_two_pass_device
+TRAY_DENOISE_RADIUS_T2 = 3   # ... and of tray_denoise_temporal_two_pass_device in the neighbouring frames
 
 
 class TrayError(RuntimeError):
@@ -199,6 +200,17 @@ SYMBOLS = {
     "tray_denoise_temporal_demodulated_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p),
                                                            _P(C.c_void_p), _P(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
                                                            C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_halves_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_halves_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p), _P(C.c_void_p), C.c_uint32,
+                                                       C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_guided_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_guided_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p),
+                                                       _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_two_pass_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_two_pass_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p), _P(C.c_void_p), C.c_uint32,
+                                                         C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]),
     "tray_denoise_guided_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "tray_denoise_guided_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -16,6 +16,7 @@
 #include "guided.h"
 #include "first_hit.h"
 #include "tdemod.h"
+#include "t2pass.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 #include "scene_plan.h"
@@ -1395,6 +1396,145 @@ int tray_denoise_temporal_demodulated_device(uint32_t width, uint32_t height, co
     for (uint32_t j = 0; j < n_neighbours; ++j) {
         tr_tdemod::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
         tr_tdemod::pass(stream, l.centre, l.neighbour, albedo_dev, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
+    }
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+// ---- the second pass over all frames (t2pass.h): tray_denoise_temporal_halves_device, _guided_device, _two_pass_device
+
+// the temporal calls' rules for (radius, radius_t, patch, k) and for N
+static int temporal_args(const std::string& who, uint32_t width, uint32_t height, uint32_t n_neighbours, uint32_t radius, uint32_t radius_t, uint32_t patch,
+                         float k) {
+    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
+    if (rc != TRAY_OK) return rc;
+    if (radius_t < 1u || radius_t > radius) { set_error(who + ": 1 <= radius_t <= radius is required"); return TRAY_E_INVALID; }
+    if (n_neighbours > TRAY_DENOISE_MAX_NEIGHBOURS) {
+        set_error(who + ": at most " + std::to_string(TRAY_DENOISE_MAX_NEIGHBOURS) + " neighbouring frames"); return TRAY_E_INVALID;
+    }
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_halves_scratch_bytes(uint32_t width, uint32_t height) { return tr_t2pass::halves_scratch_bytes(width, height); }
+
+// the 3 (N + 1) launches of the pilot over all frames into (fa, fb): l's three regions are the temporal call's
+static void temporal_halves_launches(hipStream_t stream, uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                     const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
+                                     float* fa_dev, float* fb_dev, const tr_t2pass::HalvesLayout& l) {
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.centre);
+    tr_t2pass::halves_pass(stream, l.centre, l.centre, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, fa_dev, fb_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
+        tr_t2pass::halves_pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, fa_dev, fb_dev);
+    }
+}
+
+int tray_denoise_temporal_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                        const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch,
+                                        float k, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_temporal_halves_device");
+    if (!even_dev || !odd_dev || !fa_dev || !fb_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
+    if (rc != TRAY_OK) return rc;
+    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const void* bufs[2u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 3u] = {even_dev, odd_dev, fa_dev, fb_dev, scratch_dev};
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        if (!nb_even_dev[j] || !nb_odd_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
+        bufs[5u + 2u * j] = nb_even_dev[j];
+        bufs[6u + 2u * j] = nb_odd_dev[j];
+    }
+    if (!distinct_aligned(bufs, 5u + 2u * n_neighbours)) {
+        set_error(who + ": every frame's two films, the two outputs and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    temporal_halves_launches(static_cast<hipStream_t>(stream_), width, height, even_dev, odd_dev, n_neighbours, nb_even_dev, nb_odd_dev, radius, radius_t, patch, k,
+                             fa_dev, fb_dev, tr_t2pass::halves_layout(scratch_dev, width, height));
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_guided_scratch_bytes(uint32_t width, uint32_t height) { return tr_t2pass::guided_scratch_bytes(width, height); }
+
+int tray_denoise_temporal_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* guide_a_dev,
+                                        const float* guide_b_dev, uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                        const float* const* nb_guide_a_dev, const float* const* nb_guide_b_dev, uint32_t radius, uint32_t radius_t,
+                                        uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_temporal_guided_device");
+    if (!even_dev || !odd_dev || !guide_a_dev || !guide_b_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
+    if (rc != TRAY_OK) return rc;
+    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev || !nb_guide_a_dev || !nb_guide_b_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    for (uint32_t j = 0; j < n_neighbours; ++j)
+        if (!nb_even_dev[j] || !nb_odd_dev[j] || !nb_guide_a_dev[j] || !nb_guide_b_dev[j]) {
+            set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID;
+        }
+    // the inputs are only read: a frame's guide may be its own films (then the call is tray_denoise_temporal_device); the two films of a pair
+    // differ, and the output and the scratch buffer differ from every film and from each other
+    bool ok = out_dev != scratch_dev && ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(scratch_dev)) & 15u) == 0u;
+    for (uint32_t j = 0; j <= n_neighbours; ++j) {
+        const void* const in[4] = {j ? nb_even_dev[j - 1u] : even_dev, j ? nb_odd_dev[j - 1u] : odd_dev, j ? nb_guide_a_dev[j - 1u] : guide_a_dev,
+                                   j ? nb_guide_b_dev[j - 1u] : guide_b_dev};
+        ok = ok && in[0] != in[1] && in[2] != in[3];
+        for (const void* f : in) ok = ok && (reinterpret_cast<uintptr_t>(f) & 15u) == 0u && f != out_dev && f != scratch_dev;
+    }
+    if (!ok) {
+        set_error(who + ": a frame's two films must differ, its two guide films must differ, the output and the scratch buffer must differ from every "
+                        "film and from each other, and all must be 16-byte aligned");
+        return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_t2pass::GuidedLayout l = tr_t2pass::guided_layout(scratch_dev, width, height);
+    // the centre's window first, then every neighbour's in the caller's order: per frame prepare of the values, prepare of the guide, one pass
+    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
+    tr_denoise::prepare(stream, guide_a_dev, guide_b_dev, width, height, l.centre_guide);
+    tr_t2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.values, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, out_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.values);
+        tr_denoise::prepare(stream, nb_guide_a_dev[j], nb_guide_b_dev[j], width, height, l.guide);
+        tr_t2pass::guided_pass(stream, l.centre_guide, l.guide, l.values, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
+    }
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return tr_t2pass::two_pass_scratch_bytes(width, height); }
+
+int tray_denoise_temporal_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
+                                          const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch,
+                                          float k, uint32_t radius2, uint32_t radius_t2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev,
+                                          void* stream_) {
+    const std::string who("tray_denoise_temporal_two_pass_device");
+    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
+    if (rc != TRAY_OK) return rc;
+    rc = temporal_args(who + ", second pass", width, height, n_neighbours, radius2, radius_t2, patch2, k2);
+    if (rc != TRAY_OK) return rc;
+    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    const void* bufs[2u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 2u] = {even_dev, odd_dev, out_dev, scratch_dev};
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        if (!nb_even_dev[j] || !nb_odd_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
+        bufs[4u + 2u * j] = nb_even_dev[j];
+        bufs[5u + 2u * j] = nb_odd_dev[j];
+    }
+    if (!distinct_aligned(bufs, 4u + 2u * n_neighbours)) {
+        set_error(who + ": every frame's two films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+    }
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_t2pass::TwoPassLayout l = tr_t2pass::two_pass_layout(scratch_dev, width, height);
+    // first pass: the centre's pilot over all frames (l.centre keeps the centre's records: the second pass's values of frame 0)
+    temporal_halves_launches(stream, width, height, even_dev, odd_dev, n_neighbours, nb_even_dev, nb_odd_dev, radius, radius_t, patch, k, l.fa, l.fb,
+                             tr_t2pass::HalvesLayout{l.centre, l.neighbour, l.sums});
+    // second pass: the centre guided by that pilot, then every neighbour guided by its own single-frame pilot, one at a time -- its records are
+    // resolved again (the first pass's are overwritten by the next neighbour's), and (fa, fb) is free once the pilot before it is resolved
+    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.centre_guide);
+    tr_t2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.centre, width, height, radius2, patch2, k2, l.sums, true, n_neighbours == 0u, out_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
+        tr_guide::halves(stream, l.neighbour, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
+        tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
+        tr_t2pass::guided_pass(stream, l.centre_guide, l.guide, l.neighbour, width, height, radius_t2, patch2, k2, l.sums, false, j + 1u == n_neighbours, out_dev);
     }
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;

@@ -639,6 +639,53 @@ int tray_denoise_temporal_two_pass_device(uint32_t width, uint32_t height, const
                                           uint32_t patch, float k, uint32_t radius2, uint32_t radius_t2, uint32_t patch2, float k2, float* out_dev,
                                           void* scratch_dev, void* stream);
 
+/* The two-pass temporal filter on albedo-demodulated films: the three calls above in the domain of tray_denoise_temporal_demodulated_device.
+ * Frame j (0 = the centre) has values (E_j, O_j) and an albedo film ALB_j (albedo_dev, nb_albedo_dev[j - 1]); s_j and the demodulated films
+ * E'_j = (E_j.rgb / s_j, E_j.w), O'_j likewise, are those of tray_denoise_temporal_demodulated_device; E' and O' are never written to memory.
+ *
+ * tray_denoise_temporal_demodulated_halves_device: (fa, fb) = tray_denoise_temporal_halves_device(E'_0, O'_0, N, E'_1 ..., O'_1 ..., radius,
+ * radius_t, patch, k), bit for bit. The halves are NOT multiplied by s_0: they are guides and stay in the domain the second pass measures in.
+ * With N = 0 they are a frame's own single-frame halves in that domain. 128 bytes of scratch per pixel and 3 (N + 1) launches, as there.
+ *
+ * tray_denoise_temporal_demodulated_guided_device: D = tray_denoise_temporal_guided_device(values (E'_j, O'_j), guides (GA_j, GB_j) as the
+ * caller gives them -- already in the demodulated domain, e.g. the halves call's films --, radius, radius_t, patch, k); out = (D.rgb * s_0, 1),
+ * bit for bit. 176 bytes of scratch per pixel and 5 (N + 1) launches, as there.
+ *
+ * tray_denoise_temporal_demodulated_two_pass_device: by definition D = tray_denoise_temporal_two_pass_device(E'_0, O'_0, N, E'_1 ..., O'_1 ...,
+ * radius, radius_t, patch, k, radius2, radius_t2, patch2, k2) and out = (D.rgb * s_0, 1); the output is what those three steps give one after
+ * the other, bit for bit. It is also the guided call above with the guides (fa_0, fb_0) = the halves call above over all frames and (fa_j, fb_j)
+ * = the halves call above of frame j alone (N = 0), bit for bit. With N = 0 it is tray_denoise_demodulated_device's output with radius2 >= 1;
+ * with albedo films without a valid pixel it is tray_denoise_temporal_two_pass_device's (x / 1 and x * 1 are exact). 256 bytes of scratch per
+ * pixel, laid out as there, and 9 N + 6 launches in that call's order: the demodulation is folded into the first preparing launch of every
+ * frame's films, the remodulation into the store of the last guided pass.
+ *
+ * All three: f32, unfused, IEEE division, no atomics: the same bits in every run. The *_scratch_bytes functions return 0 if width or height
+ * is 0. nb_* are HOST arrays of n_neighbours device pointers, read during the call; they may be null only when n_neighbours is 0. Every launch
+ * runs on `stream`, asynchronous, no host synchronisation, on the current device (tray_init).
+ * Return TRAY_E_INVALID, before any device call, under the rules of the call of the same name without `_demodulated` for width, height, the
+ * filter parameters and n_neighbours; if a film, an albedo film, an output or scratch_dev is null; unless all films of all frames -- 3 (N + 1)
+ * in the halves and the two-pass call, 5 (N + 1) in the guided call, whose guides may NOT alias the values --, the outputs and scratch_dev are
+ * pairwise different buffers, 16-byte aligned. */
+uint64_t tray_denoise_temporal_demodulated_halves_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_demodulated_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev,
+                                                    const float* albedo_dev, uint32_t n_neighbours, const float* const* nb_even_dev,
+                                                    const float* const* nb_odd_dev, const float* const* nb_albedo_dev, uint32_t radius,
+                                                    uint32_t radius_t, uint32_t patch, float k, float* fa_dev, float* fb_dev, void* scratch_dev,
+                                                    void* stream);
+uint64_t tray_denoise_temporal_demodulated_guided_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_demodulated_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev,
+                                                    const float* albedo_dev, const float* guide_a_dev, const float* guide_b_dev, uint32_t n_neighbours,
+                                                    const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                                    const float* const* nb_albedo_dev, const float* const* nb_guide_a_dev,
+                                                    const float* const* nb_guide_b_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
+                                                    float* out_dev, void* scratch_dev, void* stream);
+uint64_t tray_denoise_temporal_demodulated_two_pass_scratch_bytes(uint32_t width, uint32_t height);
+int tray_denoise_temporal_demodulated_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev,
+                                                      const float* albedo_dev, uint32_t n_neighbours, const float* const* nb_even_dev,
+                                                      const float* const* nb_odd_dev, const float* const* nb_albedo_dev, uint32_t radius,
+                                                      uint32_t radius_t, uint32_t patch, float k, uint32_t radius2, uint32_t radius_t2, uint32_t patch2,
+                                                      float k2, float* out_dev, void* scratch_dev, void* stream);
+
 /* tray_render_noise_target_device with the stopping rule on the image that will be shown: the rounds, the even / odd split, n_t, the outputs,
  * TrayKernelTiming and the error returns are that call's, word for word, and the films it returns are still the unfiltered films of exactly
  * [0, n_t) of every tile. One thing differs: the error of a tile in a round is that call's metric evaluated on (fa, fb) =

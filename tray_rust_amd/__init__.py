@@ -639,6 +639,123 @@ class Hip:
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
         return out
 
+    def _denoise_temporal_demodulated_halves_device(self, centre, neighbours, radius, radius_t, patch, k, into=None):
+        """tray_denoise_temporal_demodulated_halves_device of (even, odd, albedo) triples of tensors of this device on the current stream; returns
+        (fa, fb), written into `into` if given"""
+        import torch
+        e, o, a = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(3)])
+        with torch.cuda.device(self.device):
+            fa, fb = into if into is not None else (torch.empty_like(e), torch.empty_like(e))
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_demodulated_halves_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_demodulated_halves_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(a.data_ptr()),
+                                                                        len(neighbours), *arrays, int(radius), int(radius_t), int(patch), float(k),
+                                                                        C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()),
+                                                                        C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return fa, fb
+
+    def _denoise_temporal_demodulated_guided_device(self, centre, neighbours, radius, radius_t, patch, k):
+        """tray_denoise_temporal_demodulated_guided_device of (even, odd, albedo, guide_a, guide_b) tuples of tensors of this device on the current
+        stream; returns the output tensor"""
+        import torch
+        e, o, a, ga, gb = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(5)])
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_demodulated_guided_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_demodulated_guided_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(a.data_ptr()),
+                                                                        C.c_void_p(ga.data_ptr()), C.c_void_p(gb.data_ptr()), len(neighbours), *arrays,
+                                                                        int(radius), int(radius_t), int(patch), float(k), C.c_void_p(out.data_ptr()),
+                                                                        C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return out
+
+    def _denoise_temporal_demodulated_two_pass_device(self, centre, neighbours, radius, radius_t, patch, k, second):
+        """tray_denoise_temporal_demodulated_two_pass_device of (even, odd, albedo) triples of tensors of this device on the current stream; second:
+        (radius2, radius_t2, patch2, k2); returns the output tensor"""
+        import torch
+        e, o, a = centre
+        h, w = int(e.shape[0]), int(e.shape[1])
+        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(3)])
+        radius2, radius_t2, patch2, k2 = second
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(e)
+            scratch = torch.empty(max(int(lib().tray_denoise_temporal_demodulated_two_pass_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(lib().tray_denoise_temporal_demodulated_two_pass_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(a.data_ptr()),
+                                                                          len(neighbours), *arrays, int(radius), int(radius_t), int(patch), float(k),
+                                                                          int(radius2), int(radius_t2), int(patch2), float(k2), C.c_void_p(out.data_ptr()),
+                                                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return out
+
+    def _triples_on_device(self, what, frames, albedos, centre):
+        """(as_numpy, (even, odd, albedo) triples with frames[centre] first): _frames_on_device with one albedo film per frame, of the frames' kind
+        and size"""
+        frames, albedos = list(frames), list(albedos)
+        as_numpy, pairs = self._frames_on_device(what, frames, centre)
+        if len(albedos) != len(frames):
+            raise ValueError(f"{what}: albedos must hold one albedo film per frame")
+        if any(isinstance(a, np.ndarray) != as_numpy for a in albedos):
+            raise TypeError(f"{what}: the frames and the albedo films must all be numpy arrays or all be torch tensors")
+        alb = [self._film_on_device(what, a) for a in albedos]
+        if any(a.shape != pairs[0][0].shape for a in alb):
+            raise ValueError(f"{what}: the albedo films must have the frames' size")
+        c = int(centre)
+        return as_numpy, [pair + (a,) for pair, a in zip(pairs, [alb[c]] + alb[:c] + alb[c + 1:])]
+
+    def denoise_temporal_demodulated_halves(self, frames, albedos, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
+                                            patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
+        """denoise_temporal_halves() of the frames divided by their own albedo films (tray_denoise_temporal_demodulated_halves_device): frames and
+        albedos in as for denoise_temporal_demodulated(), two films out. The halves are NOT multiplied by the centre's texture: they are the
+        guides of denoise_temporal_demodulated_guided(). A one-element list gives a frame's own halves in that domain."""
+        as_numpy, triples = self._triples_on_device("denoise_temporal_demodulated_halves", frames, albedos, centre)
+        fa, fb = self._denoise_temporal_demodulated_halves_device(triples[0], triples[1:], radius, radius_t, patch, k)
+        return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
+
+    def denoise_temporal_demodulated_guided(self, frames, albedos, guides, centre, radius=_lib.TRAY_DENOISE_RADIUS2, radius_t=_lib.TRAY_DENOISE_RADIUS_T2,
+                                            patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
+        """denoise_temporal_guided() of the frames divided by their own albedo films, times frames[centre]'s texture
+        (tray_denoise_temporal_demodulated_guided_device): `guides` holds one (guide_a, guide_b) pair per frame, already in the demodulated domain,
+        e.g. denoise_temporal_demodulated_halves() of the centre and of every other frame alone. All films of one kind and size, all different."""
+        frames, guides = list(frames), list(guides)
+        what = "denoise_temporal_demodulated_guided"
+        if len(guides) != len(frames):
+            raise ValueError(f"{what}: guides must hold one pair of films per frame")
+        as_numpy, triples = self._triples_on_device(what, frames, albedos, centre)
+        guide_numpy, gpairs = self._frames_on_device(what, guides, centre)
+        if guide_numpy != as_numpy:
+            raise TypeError(f"{what}: the frames and the guides must all be numpy arrays or all be torch tensors")
+        if gpairs[0][0].shape != triples[0][0].shape:
+            raise ValueError(f"{what}: the guides must have the frames' size")
+        both = [fr + g for fr, g in zip(triples, gpairs)]
+        out = self._denoise_temporal_demodulated_guided_device(both[0], both[1:], radius, radius_t, patch, k)
+        return out.cpu().numpy() if as_numpy else out
+
+    def denoise_temporal_demodulated(self, frames, albedos, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
+                                     patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, passes=2, radius2=_lib.TRAY_DENOISE_RADIUS2,
+                                     radius_t2=_lib.TRAY_DENOISE_RADIUS_T2, patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2):
+        """denoise_temporal() on albedo-demodulated films with a second pass over all frames, for a textured, moving sequence: `frames` and `albedos`
+        as denoise_temporal(albedos=...) takes them, numpy arrays or tensors of this device, the same kind out. Every frame's colour is divided by
+        its own albedo, the remainders are filtered as denoise_temporal(passes=2) filters films, and frames[centre]'s texture is multiplied back
+        in (tray_denoise_temporal_demodulated_two_pass_device). passes=1 is denoise_temporal(albedos=...), to the bit
+        (tray_denoise_temporal_demodulated_device). A one-element list gives denoise(albedo=..., passes=2)'s image to the bit."""
+        second = self._second_pass("denoise_temporal_demodulated", passes, radius2, patch2, k2)
+        as_numpy, triples = self._triples_on_device("denoise_temporal_demodulated", frames, albedos, centre)
+        if second is None:
+            out = self._denoise_temporal_device(triples[0][:2], [t[:2] for t in triples[1:]], radius, radius_t, patch, k, [t[2] for t in triples])
+        else:
+            out = self._denoise_temporal_demodulated_two_pass_device(triples[0], triples[1:], radius, radius_t, patch, k, (radius2, radius_t2, patch2, k2))
+        return out.cpu().numpy() if as_numpy else out
+
     def _frames_on_device(self, what, frames, centre):
         """(as_numpy, pairs with frames[centre] first): a list of (even, odd) pairs of one kind and size as tensors of this device"""
         frames = list(frames)
@@ -778,6 +895,67 @@ class Hip:
                 else:
                     out = self._denoise_temporal_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k,
                                                         *(([held[g][2] for g in [f] + others],) if demodulate else ()))
+                for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
+                    spare.append(held.pop(g))
+                yield f, out.cpu().numpy()
+
+    def render_sequence_demodulated(self, scene, config, frames, reach=1, passes=2, feature_spp=None, radius=_lib.TRAY_DENOISE_RADIUS,
+                                    radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K,
+                                    radius2=_lib.TRAY_DENOISE_RADIUS2, radius_t2=_lib.TRAY_DENOISE_RADIUS_T2, patch2=_lib.TRAY_DENOISE_PATCH2,
+                                    k2=_lib.TRAY_DENOISE_K2):
+        """render_sequence_denoised() with albedo demodulation AND the second pass over all frames, for a textured, moving sequence: a generator over
+        the consecutive frame numbers `frames` that yields (frame, rgbw). Every frame is rendered once -- its two half films as there, its
+        first-hit albedo film from the samples [0, feature_spp or spp) --, its own demodulated first-pass halves are computed once, when it is
+        rendered (denoise_temporal_demodulated_halves of the frame alone), and every frame is filtered as
+        denoise_temporal_demodulated(passes=2) filters the films rendered here, to the bit: the centre's halves over its window's frames, then
+        denoise_temporal_demodulated_guided. Films held on the device: at most 5 (2 reach + 1) -- per frame of the window its two half films, its
+        albedo film and its two halves, rendered into again when the frame is done --, one throw-away normal and depth film and one pair for the
+        centre's halves over all frames: 10 reach + 9. passes=1 is render_sequence_denoised(demodulate=True). LowDiscrepancy only (TrayError
+        TRAY_E_UNSUPPORTED otherwise)."""
+        import torch
+        second = self._second_pass("render_sequence_demodulated", passes, radius2, patch2, k2)
+        if second is None:
+            yield from self.render_sequence_denoised(scene, config, frames, reach, radius, radius_t, patch, k, demodulate=True, feature_spp=feature_spp)
+            return
+        frames, reach = [int(f) for f in frames], int(reach)
+        if any(b != a + 1 for a, b in zip(frames, frames[1:])):
+            raise ValueError("render_sequence_demodulated: frames must be consecutive frame numbers")
+        if not 0 <= 2 * reach <= _lib.TRAY_DENOISE_MAX_NEIGHBOURS:
+            raise ValueError(f"render_sequence_demodulated: 0 <= reach <= {_lib.TRAY_DENOISE_MAX_NEIGHBOURS // 2}")
+        if not frames:
+            return
+        spp = self._select_sampler(scene.device_scene(frames[0], self.device), config.spp)
+        if spp < 2:
+            raise ValueError("render_sequence_demodulated: two half films need spp >= 2")
+        n_feat = spp if feature_spp is None else int(feature_spp)
+        if not 1 <= n_feat <= spp:
+            raise ValueError(f"render_sequence_demodulated: feature_spp must lie in [1, {spp}]")
+        film = scene.flatten(frames[0]).contents.film
+        w, h = int(film.width), int(film.height)
+        held, spare = {}, []   # frame -> its (even, odd, albedo, fa, fb) on the device; the films of frames that are done, to be rendered into again
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            new_film = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+            throw_away = (new_film(), new_film())   # the normal and depth films nobody reads
+            pilot = (new_film(), new_film())   # the halves of the frame in hand over all its frames
+            for f in frames:
+                window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
+                for g in window:
+                    if g not in held:
+                        films = spare.pop() if spare else tuple(new_film() for _ in range(5))
+                        for half, rng in zip(films, ((0, spp // 2), (spp // 2, spp))):
+                            half.zero_()
+                            self.render_samples_device(scene, g, config.select_blocks, spp, rng, half.data_ptr(), stream or None)
+                        for t in (films[2],) + throw_away:
+                            t.zero_()
+                        self.render_first_hit_device(scene, g, config.select_blocks, spp, (0, n_feat), films[2].data_ptr(), throw_away[0].data_ptr(),
+                                                     throw_away[1].data_ptr(), stream or None)
+                        # the frame's own demodulated first-pass halves, once: the guide it brings to its neighbours' second passes
+                        self._denoise_temporal_demodulated_halves_device(films[:3], [], radius, radius_t, patch, k, films[3:])
+                        held[g] = films
+                others = [g for g in window if g != f]
+                self._denoise_temporal_demodulated_halves_device(held[f][:3], [held[g][:3] for g in others], radius, radius_t, patch, k, pilot)
+                out = self._denoise_temporal_demodulated_guided_device(held[f][:3] + pilot, [held[g] for g in others], radius2, radius_t2, patch2, k2)
                 for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
                     spare.append(held.pop(g))
                 yield f, out.cpu().numpy()

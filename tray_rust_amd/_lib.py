@@ -211,6 +211,18 @@ SYMBOLS = {
     "tray_denoise_temporal_two_pass_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p), _P(C.c_void_p), C.c_uint32,
                                                          C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
                                                          C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_demodulated_halves_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_demodulated_halves_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p),
+                                                                  _P(C.c_void_p), _P(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,
+                                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_demodulated_guided_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_demodulated_guided_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                                  _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), C.c_uint32,
+                                                                  C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tray_denoise_temporal_demodulated_two_pass_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "tray_denoise_temporal_demodulated_two_pass_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _P(C.c_void_p),
+                                                                    _P(C.c_void_p), _P(C.c_void_p), C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32,
+                                                                    C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tray_denoise_guided_scratch_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
     "tray_denoise_guided_device": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,6 +17,7 @@
 #include "first_hit.h"
 #include "tdemod.h"
 #include "t2pass.h"
+#include "td2pass.h"
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 #include "scene_plan.h"
@@ -1535,6 +1536,141 @@ int tray_denoise_temporal_two_pass_device(uint32_t width, uint32_t height, const
         tr_guide::halves(stream, l.neighbour, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
         tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
         tr_t2pass::guided_pass(stream, l.centre_guide, l.guide, l.neighbour, width, height, radius_t2, patch2, k2, l.sums, false, j + 1u == n_neighbours, out_dev);
+    }
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+// ---- the two-pass temporal filter on albedo-demodulated films (td2pass.h): tray_denoise_temporal_demodulated_halves_device, _guided_device,
+// _two_pass_device
+
+// what the three calls refuse about their buffers: `fixed` holds the centre's films, the outputs and the scratch buffer (n_fixed of them, none
+// null), `nb` the n_arrays host arrays of the neighbours' films; all are pairwise different and 16-byte aligned
+static int demodulated_buffers(const std::string& who, const void* const* fixed, uint32_t n_fixed, const float* const* const* nb, uint32_t n_arrays,
+                               uint32_t n_neighbours) {
+    const void* bufs[5u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 3u];
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < n_fixed; ++i) bufs[n++] = fixed[i];
+    for (uint32_t a = 0; a < n_arrays; ++a)
+        if (n_neighbours > 0u && !nb[a]) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    for (uint32_t j = 0; j < n_neighbours; ++j)
+        for (uint32_t a = 0; a < n_arrays; ++a) {
+            if (!nb[a][j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
+            bufs[n++] = nb[a][j];
+        }
+    if (!distinct_aligned(bufs, n)) {
+        set_error(who + ": every frame's films and albedo film, the outputs and the scratch buffer must be different buffers, 16-byte aligned");
+        return TRAY_E_INVALID;
+    }
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_demodulated_halves_scratch_bytes(uint32_t width, uint32_t height) { return tr_td2pass::halves_scratch_bytes(width, height); }
+
+// the 3 (N + 1) launches of the pilot over all frames' demodulated films into (fa, fb): temporal_halves_launches with tr_td2pass::prepare
+static void demodulated_halves_launches(hipStream_t stream, uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                        uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                        const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k, float* fa_dev,
+                                        float* fb_dev, const tr_t2pass::HalvesLayout& l) {
+    tr_td2pass::prepare(stream, even_dev, odd_dev, albedo_dev, width, height, l.centre);
+    tr_t2pass::halves_pass(stream, l.centre, l.centre, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, fa_dev, fb_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_td2pass::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
+        tr_t2pass::halves_pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, fa_dev, fb_dev);
+    }
+}
+
+int tray_denoise_temporal_demodulated_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                                    uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                                    const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
+                                                    float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_temporal_demodulated_halves_device");
+    if (!even_dev || !odd_dev || !albedo_dev || !fa_dev || !fb_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
+    if (rc != TRAY_OK) return rc;
+    const void* const fixed[6] = {even_dev, odd_dev, albedo_dev, fa_dev, fb_dev, scratch_dev};
+    const float* const* const nb[3] = {nb_even_dev, nb_odd_dev, nb_albedo_dev};
+    rc = demodulated_buffers(who, fixed, 6u, nb, 3u, n_neighbours);
+    if (rc != TRAY_OK) return rc;
+    HIP_CHECK(hipSetDevice(g_device));
+    demodulated_halves_launches(static_cast<hipStream_t>(stream_), width, height, even_dev, odd_dev, albedo_dev, n_neighbours, nb_even_dev, nb_odd_dev,
+                                nb_albedo_dev, radius, radius_t, patch, k, fa_dev, fb_dev, tr_t2pass::halves_layout(scratch_dev, width, height));
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_demodulated_guided_scratch_bytes(uint32_t width, uint32_t height) { return tr_td2pass::guided_scratch_bytes(width, height); }
+
+int tray_denoise_temporal_demodulated_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                                    const float* guide_a_dev, const float* guide_b_dev, uint32_t n_neighbours,
+                                                    const float* const* nb_even_dev, const float* const* nb_odd_dev, const float* const* nb_albedo_dev,
+                                                    const float* const* nb_guide_a_dev, const float* const* nb_guide_b_dev, uint32_t radius,
+                                                    uint32_t radius_t, uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream_) {
+    const std::string who("tray_denoise_temporal_demodulated_guided_device");
+    if (!even_dev || !odd_dev || !albedo_dev || !guide_a_dev || !guide_b_dev || !out_dev || !scratch_dev) {
+        set_error(who + ": null argument"); return TRAY_E_INVALID;
+    }
+    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
+    if (rc != TRAY_OK) return rc;
+    const void* const fixed[7] = {even_dev, odd_dev, albedo_dev, guide_a_dev, guide_b_dev, out_dev, scratch_dev};
+    const float* const* const nb[5] = {nb_even_dev, nb_odd_dev, nb_albedo_dev, nb_guide_a_dev, nb_guide_b_dev};
+    rc = demodulated_buffers(who, fixed, 7u, nb, 5u, n_neighbours);
+    if (rc != TRAY_OK) return rc;
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_t2pass::GuidedLayout l = tr_t2pass::guided_layout(scratch_dev, width, height);
+    // as tray_denoise_temporal_guided_device: per frame prepare of the (demodulated) values, prepare of the guide, one pass; the centre's albedo
+    // scales the last pass's output
+    tr_td2pass::prepare(stream, even_dev, odd_dev, albedo_dev, width, height, l.values);
+    tr_denoise::prepare(stream, guide_a_dev, guide_b_dev, width, height, l.centre_guide);
+    tr_td2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.values, albedo_dev, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u,
+                            out_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_td2pass::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.values);
+        tr_denoise::prepare(stream, nb_guide_a_dev[j], nb_guide_b_dev[j], width, height, l.guide);
+        tr_td2pass::guided_pass(stream, l.centre_guide, l.guide, l.values, albedo_dev, width, height, radius_t, patch, k, l.sums, false,
+                                j + 1u == n_neighbours, out_dev);
+    }
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_temporal_demodulated_two_pass_scratch_bytes(uint32_t width, uint32_t height) {
+    return tr_td2pass::two_pass_scratch_bytes(width, height);
+}
+
+int tray_denoise_temporal_demodulated_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
+                                                      uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
+                                                      const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
+                                                      uint32_t radius2, uint32_t radius_t2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev,
+                                                      void* stream_) {
+    const std::string who("tray_denoise_temporal_demodulated_two_pass_device");
+    if (!even_dev || !odd_dev || !albedo_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
+    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
+    if (rc != TRAY_OK) return rc;
+    rc = temporal_args(who + ", second pass", width, height, n_neighbours, radius2, radius_t2, patch2, k2);
+    if (rc != TRAY_OK) return rc;
+    const void* const fixed[5] = {even_dev, odd_dev, albedo_dev, out_dev, scratch_dev};
+    const float* const* const nb[3] = {nb_even_dev, nb_odd_dev, nb_albedo_dev};
+    rc = demodulated_buffers(who, fixed, 5u, nb, 3u, n_neighbours);
+    if (rc != TRAY_OK) return rc;
+    HIP_CHECK(hipSetDevice(g_device));
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const tr_t2pass::TwoPassLayout l = tr_t2pass::two_pass_layout(scratch_dev, width, height);
+    static_assert(tr_td2pass::two_pass_launches(2u) == 9u * 2u + 6u, "9 N + 6 launches: the two-pass temporal call's");
+    // tray_denoise_temporal_two_pass_device's launches, one for one: every frame's films are resolved through their albedo (tr_td2pass::prepare),
+    // the pilots -- demodulated films already -- as they are, and the last guided pass multiplies the centre's scale back in
+    demodulated_halves_launches(stream, width, height, even_dev, odd_dev, albedo_dev, n_neighbours, nb_even_dev, nb_odd_dev, nb_albedo_dev, radius, radius_t,
+                                patch, k, l.fa, l.fb, tr_t2pass::HalvesLayout{l.centre, l.neighbour, l.sums});
+    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.centre_guide);
+    tr_td2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.centre, albedo_dev, width, height, radius2, patch2, k2, l.sums, true, n_neighbours == 0u,
+                            out_dev);
+    for (uint32_t j = 0; j < n_neighbours; ++j) {
+        tr_td2pass::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
+        tr_guide::halves(stream, l.neighbour, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
+        tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
+        tr_td2pass::guided_pass(stream, l.centre_guide, l.guide, l.neighbour, albedo_dev, width, height, radius_t2, patch2, k2, l.sums, false,
+                                j + 1u == n_neighbours, out_dev);
     }
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;

@@ -1,0 +1,41 @@
+// libtrayhip_td2pass.so: the kernels of tray_denoise_temporal_demodulated_halves_device / _guided_device / _two_pass_device (td2pass_kernels.h)
+// and their launches (td2pass.h).
+//   hipcc -c td2pass.hip -o td2pass.o
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "td2pass_kernels.h"
+#include "td2pass.h"
+
+namespace tr_td2pass {
+
+uint64_t halves_scratch_bytes(uint32_t width, uint32_t height) { return td2_halves_scratch_bytes(width, height); }
+uint64_t guided_scratch_bytes(uint32_t width, uint32_t height) { return td2_guided_scratch_bytes(width, height); }
+uint64_t two_pass_scratch_bytes(uint32_t width, uint32_t height) { return td2_two_pass_scratch_bytes(width, height); }
+
+void prepare(hipStream_t stream, const float* even, const float* odd, const float* albedo, uint32_t width, uint32_t height, void* records) {
+    const float4* const e4 = reinterpret_cast<const float4*>(even);
+    const float4* const o4 = reinterpret_cast<const float4*>(odd);
+    const float4* const a4 = reinterpret_cast<const float4*>(albedo);
+    float4* const s4 = static_cast<float4*>(records);
+    const uint32_t blocks = (uint32_t)(((uint64_t)width * height + DN_PREP_BLOCK - 1u) / DN_PREP_BLOCK);
+    hipLaunchKernelGGL(k_tdm_prepare, dim3(blocks), dim3(DN_PREP_BLOCK), 0, stream, e4, o4, a4, width, height, s4);
+    // (pass 1 reads the records only: the films' pointers are not dereferenced)
+    hipLaunchKernelGGL(k_dn_prepare<1>, dim3(blocks), dim3(DN_PREP_BLOCK), 0, stream, e4, o4, width, height, s4);
+}
+
+void guided_pass(hipStream_t stream, const void* centre_guide_records, const void* guide_records, const void* value_records, const float* albedo,
+                 uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k, void* sums, bool first, bool last, float* out) {
+    const float4* const c4 = static_cast<const float4*>(centre_guide_records);
+    const float4* const g4 = static_cast<const float4*>(guide_records);
+    const float4* const v4 = static_cast<const float4*>(value_records);
+    const float4* const a4 = reinterpret_cast<const float4*>(albedo);
+    float4* const acc4 = static_cast<float4*>(sums);
+    float4* const out4 = reinterpret_cast<float4*>(out);
+    dn_with_patch(patch, [&](auto f) {
+        hipLaunchKernelGGL(k_td2_guided_pass<decltype(f)::value>, dim3(dn_tiles_x(width) * dn_tiles_y(height)), dim3(DN_BLOCK), 0, stream, c4, g4, v4, a4,
+                           width, height, radius, k, acc4, first ? 1u : 0u, last ? 1u : 0u, out4);
+    });
+}
+
+}  // namespace tr_td2pass

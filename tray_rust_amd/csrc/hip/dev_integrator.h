@@ -19,6 +19,16 @@
 #pragma once
 #include "dev_tex.h"
 
+#ifdef TR_LEAN_TILES   // the lean tile kernel (kernel_tiles.h): one sub-macro per item, so that each can be compiled and measured alone
+//   TR_LEAN_MIS_PDF_FIRST  query_stage, MIS query: Light::pdf before the BSDF eval; a sample whose direction misses the light evaluates nothing
+//                          (the instantiations without mis_ray_filter: no sphere light, whose pdf is never zero, and no specular lobes)
+// -DTR_LEAN_PICK leaves them off, for a build with the ones named on the command line.
+// (Measured and not kept, profiles/r19_lean_tiles.txt: TR_LEAN_LAST_BOUNCE, no PATH query at the last allowed bounce -- one comparison, 1.1 % slower.)
+#ifndef TR_LEAN_PICK
+#define TR_LEAN_MIS_PDF_FIRST
+#endif
+#endif
+
 namespace tr {
 
 template <int ANIM>
@@ -259,7 +269,11 @@ TR_DEV void vertex_begin(const DevScene& sc, Lane& ln, const HitRec& rec, Counte
 //   WANT_MIS    BSDF half of estimate_direct (mod.rs:141-153), may set LF_MIS (ray for stage C)
 //   WANT_PATH   path continuation (path.rs:84-110): next stage A ray, or LF_LAST
 // Returns the follow-up query.
+#ifdef TR_LEAN_MIS_PDF_FIRST   // PDF_FIRST: the caller's choice per instantiation (k_path_tiles: the kernels without mis_ray_filter); off, the text below is the base's
+template <int ANIM, int FEAT, uint32_t KM = KM_ALL, bool PDF_FIRST = false>
+#else
 template <int ANIM, int FEAT, uint32_t KM = KM_ALL>
+#endif
 TR_DEV uint32_t query_stage(const DevScene& sc, Lane& ln, uint32_t want, const f3 wo_sh) {
     const bool is_light = want == WANT_LIGHT, mis = want == WANT_MIS;
     const uint32_t flags = want == WANT_PATH ? BX_ALL : BX_NON_SPECULAR;
@@ -277,6 +291,32 @@ TR_DEV uint32_t query_stage(const DevScene& sc, Lane& ln, uint32_t want, const f
         h = bsdf_sample_head_sh<FEAT, KM>(ln.bsdf, wo_sh, flags, u0, u1, one_d);
     }
     TR_QCLK(ln, 0);
+#ifdef TR_LEAN_MIS_PDF_FIRST
+    // MIS query, non-specular sample: Light::pdf (emitter.rs:193-203) of the sampled direction BEFORE BSDF::eval / ::pdf. LF_MIS is set iff
+    // pdf > 0 && !is_black(f) && (specular || pl != 0): the same conjunction with its cheap term first -- geom_pdf reads the vertex and the
+    // direction only and has no side effects. With pl == 0 (that exact test: a NaN goes on) the sample returns WANT_PATH with no state written,
+    // whatever f and pdf would have been, so they are not evaluated; on cornell_box that is all but ~1 % of the lanes, and the vote below
+    // branches most waves past the eval pass.
+    float pl_first = 0.0f;
+    bool pl_zero = false;
+    if (PDF_FIRST && mis && h.need_eval) {
+        f3 p_l, wl;
+        if (ANIM) {
+            float x[TR_XF_WORDS];
+            instance_inv_any<ANIM>(sc, light, ln.time, ln.col, x);   // (Light::pdf needs the inverse only)
+            p_l = xf_point_affine_w(x + 12, x[24], ln.bsdf.p);
+            wl = normalized(xf_vector(x + 12, h.wi_world));
+        } else {
+            p_l = xf_point(light->inv, ln.bsdf.p);
+            wl = normalized(xf_vector(light->inv, h.wi_world));
+        }
+        pl_first = geom_pdf(light, p_l, wl);
+        if (pl_first == 0.0f) { pl_zero = true; h.need_eval = false; h.need_pdf = false; }
+    }
+#ifndef TR_HOST_EMU   // (the host emulation's votes are rendezvous of the whole wave, and the lanes here are those of one query kind: per lane the two tests are one)
+    if (!PDF_FIRST || __any(h.need_eval || h.need_pdf))
+#endif
+#endif
     if (h.need_eval || h.need_pdf) {
         const f3 wi_sh = normalized(to_shading(ln.bsdf, h.wi_world));
         bsdf_eval_pdf_sh<FEAT, KM>(ln.bsdf, wo_sh, wi_sh, flags, h.need_eval, h.need_pdf, h.f, h.pdf);
@@ -296,9 +336,17 @@ TR_DEV uint32_t query_stage(const DevScene& sc, Lane& ln, uint32_t want, const f
         return delta ? WANT_PATH : WANT_MIS;
     }
     if (mis) {
+#ifdef TR_LEAN_MIS_PDF_FIRST
+        if (pl_zero) return WANT_PATH;   // `return direct_light` (mod.rs:146-148)
+#endif
         if (pdf > 0.0f && !is_black(f)) {
             float w = 1.0f;
             if (!(h.sampled_type & BX_SPECULAR)) {
+#ifdef TR_LEAN_MIS_PDF_FIRST
+                if (PDF_FIRST) w = power_heuristic(1.0f, pdf, 1.0f, pl_first);   // (a sample with pdf > 0 is a sampled one: its pl was computed above)
+                else
+#endif
+                {
                 // Light::pdf (emitter.rs:193-203)
                 f3 p_l, wl;
                 if (ANIM) {
@@ -313,6 +361,7 @@ TR_DEV uint32_t query_stage(const DevScene& sc, Lane& ln, uint32_t want, const f
                 float pl = geom_pdf(light, p_l, wl);
                 if (pl == 0.0f) return WANT_PATH;   // `return direct_light` (mod.rs:146-148)
                 w = power_heuristic(1.0f, pdf, 1.0f, pl);
+                }
             } else ln.flags |= LF_MIS_UNTESTED;
             // direct += f * li * |cos| * w / pdf_bsdf once li is known (mod.rs:163-165): keep the factors
             ln.mis_f = f;
@@ -340,7 +389,11 @@ TR_DEV uint32_t query_stage(const DevScene& sc, Lane& ln, uint32_t want, const f
 // the three kinds of query run as three wave-aligned passes -- LIGHT for the lanes whose shadow ray was not occluded, then MIS,
 // then PATH -- so that the kind is wave-uniform inside query_stage (scalar branches; the sample head runs twice per vertex, not
 // three times as it did when occluded lanes started with MIS while the others were still at LIGHT).
+#ifdef TR_LEAN_MIS_PDF_FIRST
+template <int ANIM, int FEAT, uint32_t KM = KM_ALL, bool PDF_FIRST = false>
+#else
 template <int ANIM, int FEAT, uint32_t KM = KM_ALL>
+#endif
 TR_DEV void vertex_queries(const DevScene& sc, Lane& ln, bool occluded, bool active = true) {
     uint32_t want = WANT_NONE;
     const DevMaterial* table_mat = nullptr;
@@ -367,7 +420,11 @@ TR_DEV void vertex_queries(const DevScene& sc, Lane& ln, bool occluded, bool act
 #endif
         const bool go = want == kind;
         if (!__any(go)) continue;
+#ifdef TR_LEAN_MIS_PDF_FIRST
+        if (go) want = query_stage<ANIM, FEAT, KM, PDF_FIRST>(sc, ln, kind, wo_sh);
+#else
         if (go) want = query_stage<ANIM, FEAT, KM>(sc, ln, kind, wo_sh);
+#endif
         TR_QCLK(ln, 2);
     }
 #if defined(TR_EMU_PROFILE)

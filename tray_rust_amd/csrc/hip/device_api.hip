@@ -9,6 +9,7 @@
 #include "kernel_list.h"
 #include "kernel_select.h"   // (after the declarations: the selectors instantiate no kernel here)
 #include "kernel_ranges.h"
+#include "kernel_tiles.h"
 #include "noise.h"
 #include "denoise.h"
 #include "guide.h"
@@ -143,6 +144,7 @@ struct TrayDeviceScene {
     hipStream_t wf_streams[WF_PIPES_MAX] = {nullptr, nullptr, nullptr, nullptr};   // streams of views 1.. (view 0 runs on the caller's), created on first use
     hipEvent_t wf_fork = nullptr, wf_join[WF_PIPES_MAX] = {nullptr, nullptr, nullptr, nullptr};
     bool light_filter = false;        // a sphere light or specular lobes: the tile kernel with mis_ray_filter (dev_integrator.h) compiled in
+    bool lean_tiles = true;           // whole-frame Path launches of a static scene run libtrayhip_tiles.so's kernel (kernel_tiles.h); TRAYHIP_LEAN_TILES=0: the base kernel
     WfBinGrid bin_grid{};                // the cells of the frame's BVH<Instance> box
     bool wf_fused = true;                // fused shading between the traversals (wavefront.h: k_wf_shade_kind); TRAYHIP_WF_FUSED=0|1 overrides
     uint32_t wf_bin_stages = 0u;         // bit 0: stage A rays are binned, bit 1: stage B rays (TRAYHIP_WF_BIN overrides)
@@ -406,8 +408,14 @@ void tray_scene_destroy(TrayDeviceScene* s) {
 
 } // extern "C" (scene_build is internal)
 
+// whether a whole-frame launch of this scene runs the lean tile kernel (kernel_tiles.h): static scenes under the Path integrator
+static bool runs_lean_tiles(const TrayDeviceScene* s) {
+    return s->lean_tiles && !s->animated && s->dev.integrator != TRAY_INTEGRATOR_WHITTED;
+}
+
 // the k_path_tiles instantiation launch_tiles runs for this scene: what the occupancy is asked of
 static const void* tile_kernel(const TrayDeviceScene* s) {
+    if (runs_lean_tiles(s)) return tr_tiles::path_tiles_kernel(s->feat, s->light_filter);
     const void* k = nullptr;
     const auto take = [&](auto kernel) { k = reinterpret_cast<const void*>(kernel); };
     const bool whitted = s->dev.integrator == TRAY_INTEGRATOR_WHITTED;
@@ -520,6 +528,7 @@ static int scene_plan(const TrayFlatScene* f, TrayDeviceScene* s, const std::vec
     if (const char* e = getenv("TRAYHIP_WF_BIN")) s->wf_bin_stages = (uint32_t)std::max(0, atoi(e)) & 3u;
     s->wf_fused = WF_FUSED_DEFAULT != 0;
     if (const char* e = getenv("TRAYHIP_WF_FUSED")) s->wf_fused = atoi(e) != 0;
+    if (const char* e = getenv("TRAYHIP_LEAN_TILES")) s->lean_tiles = atoi(e) != 0;   // (0: the base kernel, for A/B runs and bisecting)
     return TRAY_OK;
 }
 
@@ -658,6 +667,8 @@ static void raise_lds_limit(uint32_t stack_bytes) {
         reinterpret_cast<const void*>(k_sampler_pass<0, FEAT_NONE>), reinterpret_cast<const void*>(k_sampler_pass<2, FEAT_NONE>), reinterpret_cast<const void*>(k_sampler_pass<3, FEAT_NONE>),
         reinterpret_cast<const void*>(k_debug_intersect<3>), reinterpret_cast<const void*>(k_debug_sample_radiance<3>)};
     for (const void* k : traversing) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stack_bytes);
+    for (const int feat : {(int)FEAT_NONE, (int)FEAT_MERL, (int)FEAT_SPEC, FEAT_MERL | FEAT_SPEC, (int)FEAT_ALL, FEAT_ALL | FEAT_TEX})   // the lean tile kernels (kernel_tiles.h)
+        for (const bool lf : {false, true}) (void)hipFuncSetAttribute(tr_tiles::path_tiles_kernel(feat, lf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stack_bytes);
     (void)hipGetLastError();
 }
 
@@ -1915,8 +1926,11 @@ static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_co
     };
     if (smp_end) tr_ranges::path_tiles(s->animated ? 1 : 0, s->feat, whitted, s->light_filter, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream,
                                        s->launch_dev, tiles, tile_count, chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats, smp_begin, smp_end);
+    else if (runs_lean_tiles(s)) tr_tiles::path_tiles(s->feat, s->light_filter, dim3(blocks), dim3(TR_BLOCK), s->stack_bytes, stream, s->launch_dev, tiles, tile_count,
+                                                      chunk, chunk_stride, spp, kf, levels, rgbw_dev, s->d_counter, s->d_stats);
     else if (s->animated) select_path_tiles<1>(s->feat, whitted, s->light_filter, launch);
     else select_path_tiles<0>(s->feat, whitted, s->light_filter, launch);
+    if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] tile launch: %s kernel\n", smp_end ? "sample-range (libtrayhip_ranges.so)" : runs_lean_tiles(s) ? "lean (libtrayhip_tiles.so)" : "base (libtrayhip.so)");
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(s->ev1, stream));
     s->timing_valid = true;

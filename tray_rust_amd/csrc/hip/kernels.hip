@@ -401,7 +401,11 @@ __global__ __launch_bounds__(TR_BLOCK, (FEAT == 15 || INTEG != TRAY_INTEGRATOR_P
                 if (stage == 0 && alive && tr_.hit) ++dump_v;
 #endif
                 if (stage == 1) {
+#ifdef TR_LEAN_MIS_PDF_FIRST   // (not under LFILT -- a sphere light, whose pdf is never zero, or specular lobes --: smallpt gains nothing from the order and was slower with it, profiles/r19_lean_tiles.txt)
+                    vertex_queries<ANIM, FEAT, KM_ALL, !LFILT>(sc, ln, tr_.hit, alive);
+#else
                     vertex_queries<ANIM, FEAT>(sc, ln, tr_.hit, alive);   // (the whole wave enters: wave-aligned query passes)
+#endif
                 } else if (alive) {
                     if (stage == 0) {
                         if (tr_.hit) vertex_begin<ANIM>(sc, ln, tr_.rec, cnt);

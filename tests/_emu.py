@@ -25,6 +25,11 @@ def device_deps():
     return deps + [os.path.join(ROOT, "tray_rust_amd", "csrc", "host", "gates.hpp"), os.path.join(ROOT, "include", "trayhip.h")]
 
 
+def denoise_plan_deps():
+    """what every denoiser emulation is compiled from besides its kernels' headers: the calls' plan, the emulation's Ops and the C header the plan reads"""
+    return [os.path.join(HIP_DIR, "denoise_plan.h"), os.path.join(EMU_DIR, "emu_denoise_ops.h"), os.path.join(ROOT, "include", "trayhip.h")]
+
+
 def _start_build(so, src, deps, defines=()):
     """(path of tests/emu/<so>, the running g++ or None): compiles it from tests/emu/<src> if it is missing or older than the source or one of deps"""
     so, src = os.path.join(EMU_DIR, so), os.path.join(EMU_DIR, src)

@@ -44,7 +44,7 @@ def noise_lib():
 
 @functools.lru_cache(None)
 def denoise_lib():
-    h = C.CDLL(E.build("libtrayemu_denoise.so", "emu_denoise.cpp", _hip("denoise_kernels.h", "dev_libm.h")))
+    h = C.CDLL(E.build("libtrayemu_denoise.so", "emu_denoise.cpp", _hip("denoise_kernels.h", "dev_libm.h") + E.denoise_plan_deps()))
     h.emu_denoise.restype = C.c_int
     h.emu_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
     h.emu_denoise_scratch_bytes.restype = C.c_uint64
@@ -54,7 +54,8 @@ def denoise_lib():
 
 @functools.lru_cache(None)
 def guide_lib():
-    h = C.CDLL(E.build("libtrayemu_guide.so", "emu_guide.cpp", _hip("guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h") + [os.path.join(E.EMU_DIR, "emu_denoise.cpp")]))
+    h = C.CDLL(E.build("libtrayemu_guide.so", "emu_guide.cpp", _hip("guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h")
+                       + [os.path.join(E.EMU_DIR, "emu_denoise.cpp")] + E.denoise_plan_deps()))
     h.emu_guide_halves.restype = C.c_int
     h.emu_guide_halves.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]

@@ -131,6 +131,7 @@ def assert_two_pass(got, even, odd, r, f, k, r2, f2, k2, what):
 def guided_lib():
     deps = [os.path.join(E.EMU_DIR, x) for x in ("hip_emu.h", "emu_denoise.cpp", "emu_guide.cpp")]
     deps += [os.path.join(E.HIP_DIR, h) for h in ("guided_kernels.h", "guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h")]
+    deps += E.denoise_plan_deps()
     h = C.CDLL(E.build("libtrayemu_guided.so", "emu_guided.cpp", deps))
     h.emu_denoise_guided.restype = C.c_int
     h.emu_denoise_guided.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p,

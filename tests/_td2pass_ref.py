@@ -128,6 +128,7 @@ def td2pass_lib():
     deps = [os.path.join(E.EMU_DIR, x) for x in ("hip_emu.h", "emu_denoise.cpp", "emu_guide.cpp", "emu_temporal2.cpp")]
     deps += [os.path.join(E.HIP_DIR, h) for h in ("td2pass_kernels.h", "tdemod_kernels.h", "t2pass_kernels.h", "guide_kernels.h", "block_compact.h",
                                                   "denoise_kernels.h", "dev_libm.h")]
+    deps += E.denoise_plan_deps() + [os.path.join(E.EMU_DIR, "denoise_plan_record.h")]
     h = C.CDLL(E.build("libtrayemu_td2pass.so", "emu_td2pass.cpp", deps))
     P = C.POINTER(C.c_void_p)
     u32, f32, ptr = C.c_uint32, C.c_float, C.c_void_p
@@ -140,6 +141,10 @@ def td2pass_lib():
     for name in ("emu_td2_halves_scratch_bytes", "emu_td2_guided_scratch_bytes", "emu_td2_two_pass_scratch_bytes"):
         getattr(h, name).restype = C.c_uint64
         getattr(h, name).argtypes = [u32, u32]
+    h.emu_denoise_plan_layout.restype = u32   # (tests/test_denoise_plan.py)
+    h.emu_denoise_plan_layout.argtypes = [u32, u32, u32, ptr, u32, ptr]
+    h.emu_denoise_plan_launches.restype = u32
+    h.emu_denoise_plan_launches.argtypes = [u32, u32]
     return h
 
 

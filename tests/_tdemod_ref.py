@@ -118,7 +118,7 @@ def same_bits(a, b):
 @functools.lru_cache(None)
 def tdemod_lib():
     deps = [os.path.join(E.EMU_DIR, "hip_emu.h")]
-    deps += [os.path.join(E.HIP_DIR, h) for h in ("tdemod_kernels.h", "denoise_kernels.h", "dev_libm.h")]
+    deps += [os.path.join(E.HIP_DIR, h) for h in ("tdemod_kernels.h", "denoise_kernels.h", "dev_libm.h")] + E.denoise_plan_deps()
     h = C.CDLL(E.build("libtrayemu_tdemod.so", "emu_tdemod.cpp", deps))
     P = C.POINTER(C.c_void_p)
     h.emu_denoise_temporal_demodulated.restype = C.c_int

@@ -153,6 +153,7 @@ def same_bits(a, b):
 def temporal2_lib():
     deps = [os.path.join(E.EMU_DIR, x) for x in ("hip_emu.h", "emu_denoise.cpp", "emu_guide.cpp")]
     deps += [os.path.join(E.HIP_DIR, h) for h in ("t2pass_kernels.h", "guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h")]
+    deps += E.denoise_plan_deps()
     h = C.CDLL(E.build("libtrayemu_temporal2.so", "emu_temporal2.cpp", deps))
     P = C.POINTER(C.c_void_p)
     u32, f32, ptr = C.c_uint32, C.c_float, C.c_void_p

@@ -135,7 +135,7 @@ def random_frames(w, h, n, seed):
 @functools.lru_cache(None)
 def temporal_lib():
     deps = [os.path.join(E.EMU_DIR, "hip_emu.h"), os.path.join(E.EMU_DIR, "emu_denoise.cpp")]
-    deps += [os.path.join(E.HIP_DIR, h) for h in ("temporal_kernels.h", "denoise_kernels.h", "dev_libm.h")]
+    deps += [os.path.join(E.HIP_DIR, h) for h in ("temporal_kernels.h", "denoise_kernels.h", "dev_libm.h")] + E.denoise_plan_deps()
     h = C.CDLL(E.build("libtrayemu_temporal.so", "emu_temporal.cpp", deps))
     h.emu_denoise_temporal.restype = C.c_int
     h.emu_denoise_temporal.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32,

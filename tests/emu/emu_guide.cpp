@@ -1,6 +1,6 @@
 // Host emulation of the kernels of the filtered stopping rule (tray_rust_amd/csrc/hip/guide_kernels.h): k_dn_filter_halves, k_guide_mark and
 // k_guide_compact, compiled by g++ behind hip_emu.h and run as SIMT fibers, so that the LDS staging, the barriers, the ballots and the
-// block-wide scan execute as the device executes them. Built by tests/test_guide_emu.py. Includes emu_denoise.cpp for its `prepare`.
+// block-wide scan execute as the device executes them. Built by tests/test_guide_emu.py. Includes emu_denoise.cpp for EmuOps.
 #include "emu_denoise.cpp"
 #include "../../tray_rust_amd/csrc/hip/guide_kernels.h"
 
@@ -8,24 +8,28 @@
 
 using namespace tr_guide;
 
+struct GuideOps : EmuOps {
+    using EmuOps::EmuOps;
+    // one k_dn_filter_halves<patch> launch as guide.hip makes it: over the list, or over every block when blocks is null
+    void halves(const void* records, uint32_t radius, uint32_t patch, float k, const uint32_t* blocks, uint32_t n_blocks, float* fa, float* fb) {
+        const float4* const s4 = emu_f4(records);
+        float4* const a4 = emu_f4(fa), * const b4 = emu_f4(fb);
+        run_tiles(blocks ? n_blocks : dn_tiles_x(width) * dn_tiles_y(height), patch,
+                  [&](auto f) { k_dn_filter_halves<decltype(f)::value>(s4, width, height, radius, k, blocks, a4, b4); });
+    }
+};
+
 extern "C" {
 
-// the launches of one tray_denoise_halves_device call, in its order (k_dn_prepare<0>, <1>, k_dn_filter_halves<patch> over the list, or over every
-// block when blocks is null); scratch: 48 bytes per pixel
+// one tray_denoise_halves_device call: the plan's schedule (k_dn_prepare<0>, <1>, k_dn_filter_halves<patch>; nothing for an empty list); scratch: 48
+// bytes per pixel
 int emu_guide_halves(const float* even, const float* odd, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k, const uint32_t* blocks,
                      uint32_t n_blocks, float* fa, float* fb, void* scratch) {
-    if (width == 0u || height == 0u || radius < 1u || radius > DN_RMAX || patch > DN_FMAX) return -2;
-    if (blocks && n_blocks == 0u) return 0;
-    float4* const s4 = static_cast<float4*>(scratch);
-    float4* const a4 = reinterpret_cast<float4*>(fa);
-    float4* const b4 = reinterpret_cast<float4*>(fb);
-    const int rc = prepare(reinterpret_cast<const float4*>(even), reinterpret_cast<const float4*>(odd), width, height, s4);
-    if (rc != 0) return rc;
-    const uint32_t grid = blocks ? n_blocks : dn_tiles_x(width) * dn_tiles_y(height);
-    return dn_with_patch(patch, [&](auto f) {
-        constexpr int F = decltype(f)::value;
-        return hip_emu::launch_simt(grid, DN_BLOCK, [&] { k_dn_filter_halves<F>(s4, width, height, radius, k, blocks, a4, b4); });
-    });
+    const dn::Params p{radius, 0u, patch, k};
+    if (emu_refused(emu_filter_args(width, height, p))) return -2;
+    GuideOps ops(width, height);
+    dn::halves(ops, dn::Frame{even, odd, nullptr, nullptr, nullptr}, p, blocks, n_blocks, fa, fb, scratch);
+    return ops.rc;
 }
 
 // one k_guide_mark launch as guide.hip makes it; queue_xy: n (x, y) pairs, active: n words or null; flags: one word per block of the frame

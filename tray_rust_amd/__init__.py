@@ -551,151 +551,44 @@ class Hip:
             rt.add_pixels(out.reshape(-1).cpu().numpy())
         return result
 
-    def _denoise_temporal_device(self, centre, neighbours, radius, radius_t, patch, k, albedos=None):
-        """tray_denoise_temporal_device of (even, odd) pairs of (h, w, 4) float32 tensors of this device on the current stream: `centre` filtered
-        with `neighbours` (a list of pairs, in order); returns the output tensor. albedos: the albedo tensors of the centre and of the neighbours,
-        in that order (tray_denoise_temporal_demodulated_device)"""
+    def _temporal_call(self, stem, centre, neighbours, first, second=None, halves=False, into=None):
+        """tray_denoise_<stem>_device on the current stream, for every temporal call: `centre` and each of `neighbours` (a list, in order) are
+        tuples of (h, w, 4) float32 tensors of this device -- (even, odd), then the albedo and / or the (guide_a, guide_b) the call takes --;
+        first and the optional second are (radius, radius_t, patch, k). Returns the output tensor, or with `halves` the pair (fa, fb), written
+        into `into` if given."""
         import torch
-        e, o = centre
+        e = centre[0]
         h, w = int(e.shape[0]), int(e.shape[1])
         n = len(neighbours)
-        array = lambda tensors: (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in tensors])
-        pointers = lambda i: array([pair[i] for pair in neighbours])
+        # host arrays of device pointers, one per film of a frame (never of length 0)
+        arrays = [(C.c_void_p * max(n, 1))(*[fr[i].data_ptr() for fr in neighbours]) for i in range(len(centre))]
+        params = [v for r, rt, f, k in ([first] if second is None else [first, second]) for v in (int(r), int(rt), int(f), float(k))]
+        pointers = lambda tensors: [C.c_void_p(t.data_ptr()) for t in tensors]
         with torch.cuda.device(self.device):
-            out = torch.empty_like(e)
-            nbytes = lib().tray_denoise_temporal_scratch_bytes if albedos is None else lib().tray_denoise_temporal_demodulated_scratch_bytes
-            scratch = torch.empty(max(int(nbytes(w, h)), 16), dtype=torch.uint8, device=e.device)
+            outs = (torch.empty_like(e),) if not halves else tuple(into) if into is not None else (torch.empty_like(e), torch.empty_like(e))
+            scratch = torch.empty(max(int(getattr(lib(), f"tray_denoise_{stem}_scratch_bytes")(w, h)), 16), dtype=torch.uint8, device=e.device)
             stream = torch.cuda.current_stream().cuda_stream
             check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            tail = (int(radius), int(radius_t), int(patch), float(k), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                    C.c_void_p(stream) if stream else None)
-            if albedos is None:
-                check(lib().tray_denoise_temporal_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), n, pointers(0), pointers(1), *tail))
-            else:
-                check(lib().tray_denoise_temporal_demodulated_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()),
-                                                                     C.c_void_p(albedos[0].data_ptr()), n, pointers(0), pointers(1), array(albedos[1:]),
-                                                                     *tail))
+            check(getattr(lib(), f"tray_denoise_{stem}_device")(w, h, *pointers(centre), n, *arrays, *params, *pointers(outs),
+                                                                 C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
             torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out
+        return outs if halves else outs[0]
 
-    def _temporal_arrays(self, lists):
-        """host arrays of device pointers, one per list of tensors (never of length 0)"""
-        return [(C.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts]) for ts in lists]
+    def _denoise_temporal_device(self, centre, neighbours, radius, radius_t, patch, k, albedos=None):
+        """tray_denoise_temporal_device of (even, odd) pairs; albedos: the albedo tensors of the centre and of the neighbours, in that order
+        (tray_denoise_temporal_demodulated_device)"""
+        if albedos is None:
+            return self._temporal_call("temporal", centre, neighbours, (radius, radius_t, patch, k))
+        triples = [tuple(pair) + (a,) for pair, a in zip([centre] + list(neighbours), albedos)]
+        return self._temporal_call("temporal_demodulated", triples[0], triples[1:], (radius, radius_t, patch, k))
 
     def _denoise_temporal_halves_device(self, centre, neighbours, radius, radius_t, patch, k, into=None):
-        """tray_denoise_temporal_halves_device of (even, odd) pairs of tensors of this device on the current stream; returns (fa, fb), written into
-        `into` if given"""
-        import torch
-        e, o = centre
-        h, w = int(e.shape[0]), int(e.shape[1])
-        nbe, nbo = self._temporal_arrays([[p[0] for p in neighbours], [p[1] for p in neighbours]])
-        with torch.cuda.device(self.device):
-            fa, fb = into if into is not None else (torch.empty_like(e), torch.empty_like(e))
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_halves_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_halves_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), len(neighbours), nbe, nbo, int(radius),
-                                                            int(radius_t), int(patch), float(k), C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()),
-                                                            C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return fa, fb
-
-    def _denoise_temporal_guided_device(self, centre, neighbours, radius, radius_t, patch, k):
-        """tray_denoise_temporal_guided_device of (even, odd, guide_a, guide_b) tuples of tensors of this device on the current stream; returns the
-        output tensor"""
-        import torch
-        e, o, ga, gb = centre
-        h, w = int(e.shape[0]), int(e.shape[1])
-        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(4)])
-        with torch.cuda.device(self.device):
-            out = torch.empty_like(e)
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_guided_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_guided_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(ga.data_ptr()),
-                                                            C.c_void_p(gb.data_ptr()), len(neighbours), *arrays, int(radius), int(radius_t), int(patch),
-                                                            float(k), C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                                                            C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out
-
-    def _denoise_temporal_two_pass_device(self, centre, neighbours, radius, radius_t, patch, k, second):
-        """tray_denoise_temporal_two_pass_device of (even, odd) pairs of tensors of this device on the current stream; second: (radius2, radius_t2,
-        patch2, k2); returns the output tensor"""
-        import torch
-        e, o = centre
-        h, w = int(e.shape[0]), int(e.shape[1])
-        nbe, nbo = self._temporal_arrays([[p[0] for p in neighbours], [p[1] for p in neighbours]])
-        radius2, radius_t2, patch2, k2 = second
-        with torch.cuda.device(self.device):
-            out = torch.empty_like(e)
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_two_pass_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_two_pass_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), len(neighbours), nbe, nbo, int(radius),
-                                                              int(radius_t), int(patch), float(k), int(radius2), int(radius_t2), int(patch2), float(k2),
-                                                              C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                                                              C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out
+        """tray_denoise_temporal_halves_device of (even, odd) pairs; returns (fa, fb), written into `into` if given"""
+        return self._temporal_call("temporal_halves", centre, neighbours, (radius, radius_t, patch, k), halves=True, into=into)
 
     def _denoise_temporal_demodulated_halves_device(self, centre, neighbours, radius, radius_t, patch, k, into=None):
-        """tray_denoise_temporal_demodulated_halves_device of (even, odd, albedo) triples of tensors of this device on the current stream; returns
-        (fa, fb), written into `into` if given"""
-        import torch
-        e, o, a = centre
-        h, w = int(e.shape[0]), int(e.shape[1])
-        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(3)])
-        with torch.cuda.device(self.device):
-            fa, fb = into if into is not None else (torch.empty_like(e), torch.empty_like(e))
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_demodulated_halves_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_demodulated_halves_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(a.data_ptr()),
-                                                                        len(neighbours), *arrays, int(radius), int(radius_t), int(patch), float(k),
-                                                                        C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()),
-                                                                        C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return fa, fb
-
-    def _denoise_temporal_demodulated_guided_device(self, centre, neighbours, radius, radius_t, patch, k):
-        """tray_denoise_temporal_demodulated_guided_device of (even, odd, albedo, guide_a, guide_b) tuples of tensors of this device on the current
-        stream; returns the output tensor"""
-        import torch
-        e, o, a, ga, gb = centre
-        h, w = int(e.shape[0]), int(e.shape[1])
-        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(5)])
-        with torch.cuda.device(self.device):
-            out = torch.empty_like(e)
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_demodulated_guided_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_demodulated_guided_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(a.data_ptr()),
-                                                                        C.c_void_p(ga.data_ptr()), C.c_void_p(gb.data_ptr()), len(neighbours), *arrays,
-                                                                        int(radius), int(radius_t), int(patch), float(k), C.c_void_p(out.data_ptr()),
-                                                                        C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out
-
-    def _denoise_temporal_demodulated_two_pass_device(self, centre, neighbours, radius, radius_t, patch, k, second):
-        """tray_denoise_temporal_demodulated_two_pass_device of (even, odd, albedo) triples of tensors of this device on the current stream; second:
-        (radius2, radius_t2, patch2, k2); returns the output tensor"""
-        import torch
-        e, o, a = centre
-        h, w = int(e.shape[0]), int(e.shape[1])
-        arrays = self._temporal_arrays([[fr[i] for fr in neighbours] for i in range(3)])
-        radius2, radius_t2, patch2, k2 = second
-        with torch.cuda.device(self.device):
-            out = torch.empty_like(e)
-            scratch = torch.empty(max(int(lib().tray_denoise_temporal_demodulated_two_pass_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_temporal_demodulated_two_pass_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(a.data_ptr()),
-                                                                          len(neighbours), *arrays, int(radius), int(radius_t), int(patch), float(k),
-                                                                          int(radius2), int(radius_t2), int(patch2), float(k2), C.c_void_p(out.data_ptr()),
-                                                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out
+        """tray_denoise_temporal_demodulated_halves_device of (even, odd, albedo) triples; returns (fa, fb), written into `into` if given"""
+        return self._temporal_call("temporal_demodulated_halves", centre, neighbours, (radius, radius_t, patch, k), halves=True, into=into)
 
     def _triples_on_device(self, what, frames, albedos, centre):
         """(as_numpy, (even, odd, albedo) triples with frames[centre] first): _frames_on_device with one albedo film per frame, of the frames' kind
@@ -737,7 +630,7 @@ class Hip:
         if gpairs[0][0].shape != triples[0][0].shape:
             raise ValueError(f"{what}: the guides must have the frames' size")
         both = [fr + g for fr, g in zip(triples, gpairs)]
-        out = self._denoise_temporal_demodulated_guided_device(both[0], both[1:], radius, radius_t, patch, k)
+        out = self._temporal_call("temporal_demodulated_guided", both[0], both[1:], (radius, radius_t, patch, k))
         return out.cpu().numpy() if as_numpy else out
 
     def denoise_temporal_demodulated(self, frames, albedos, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
@@ -751,9 +644,9 @@ class Hip:
         second = self._second_pass("denoise_temporal_demodulated", passes, radius2, patch2, k2)
         as_numpy, triples = self._triples_on_device("denoise_temporal_demodulated", frames, albedos, centre)
         if second is None:
-            out = self._denoise_temporal_device(triples[0][:2], [t[:2] for t in triples[1:]], radius, radius_t, patch, k, [t[2] for t in triples])
+            out = self._temporal_call("temporal_demodulated", triples[0], triples[1:], (radius, radius_t, patch, k))
         else:
-            out = self._denoise_temporal_demodulated_two_pass_device(triples[0], triples[1:], radius, radius_t, patch, k, (radius2, radius_t2, patch2, k2))
+            out = self._temporal_call("temporal_demodulated_two_pass", triples[0], triples[1:], (radius, radius_t, patch, k), (radius2, radius_t2, patch2, k2))
         return out.cpu().numpy() if as_numpy else out
 
     def _frames_on_device(self, what, frames, centre):
@@ -795,7 +688,7 @@ class Hip:
         if gpairs[0][0].shape != pairs[0][0].shape:
             raise ValueError("denoise_temporal_guided: the guides must have the frames' size")
         both = [fr + g for fr, g in zip(pairs, gpairs)]
-        out = self._denoise_temporal_guided_device(both[0], both[1:], radius, radius_t, patch, k)
+        out = self._temporal_call("temporal_guided", both[0], both[1:], (radius, radius_t, patch, k))
         return out.cpu().numpy() if as_numpy else out
 
     def denoise_temporal(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
@@ -817,7 +710,7 @@ class Hip:
         as_numpy, pairs = self._frames_on_device("denoise_temporal", frames, centre)
         c = int(centre)
         if second is not None:
-            out = self._denoise_temporal_two_pass_device(pairs[0], pairs[1:], radius, radius_t, patch, k, (radius2, radius_t2, patch2, k2))
+            out = self._temporal_call("temporal_two_pass", pairs[0], pairs[1:], (radius, radius_t, patch, k), (radius2, radius_t2, patch2, k2))
         elif albedos is None:
             out = self._denoise_temporal_device(pairs[0], pairs[1:], radius, radius_t, patch, k)
         else:
@@ -891,7 +784,7 @@ class Hip:
                 others = [g for g in window if g != f]
                 if second is not None:
                     self._denoise_temporal_halves_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k, pilot)
-                    out = self._denoise_temporal_guided_device(held[f][:2] + pilot, [held[g] for g in others], radius2, radius_t2, patch2, k2)
+                    out = self._temporal_call("temporal_guided", held[f][:2] + pilot, [held[g] for g in others], (radius2, radius_t2, patch2, k2))
                 else:
                     out = self._denoise_temporal_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k,
                                                         *(([held[g][2] for g in [f] + others],) if demodulate else ()))
@@ -955,7 +848,7 @@ class Hip:
                         held[g] = films
                 others = [g for g in window if g != f]
                 self._denoise_temporal_demodulated_halves_device(held[f][:3], [held[g][:3] for g in others], radius, radius_t, patch, k, pilot)
-                out = self._denoise_temporal_demodulated_guided_device(held[f][:3] + pilot, [held[g] for g in others], radius2, radius_t2, patch2, k2)
+                out = self._temporal_call("temporal_demodulated_guided", held[f][:3] + pilot, [held[g] for g in others], (radius2, radius_t2, patch2, k2))
                 for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
                     spare.append(held.pop(g))
                 yield f, out.cpu().numpy()

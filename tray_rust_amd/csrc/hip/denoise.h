@@ -8,8 +8,6 @@ constexpr uint32_t kLaunches = 3u;
 // the first two launches of denoise(): k_dn_prepare<0> and <1> resolve the films into the scratch records that k_dn_filter and k_dn_filter_halves read
 constexpr uint32_t kPrepareLaunches = 2u;
 void prepare(hipStream_t stream, const float* even, const float* odd, uint32_t width, uint32_t height, void* scratch);
-// bytes of scratch denoise() needs for a width x height film
-uint64_t scratch_bytes(uint32_t width, uint32_t height);
 // out = the filter of even / odd (width * height RGBW pixels each, 16-byte aligned like scratch); 1 <= radius <= 10, patch <= 3, width, height >= 1
 void denoise(hipStream_t stream, const float* even, const float* odd, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k, float* out,
              void* scratch);

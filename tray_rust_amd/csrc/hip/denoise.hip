@@ -8,8 +8,6 @@
 
 namespace tr_denoise {
 
-uint64_t scratch_bytes(uint32_t width, uint32_t height) { return dn_scratch_bytes(width, height); }
-
 void prepare(hipStream_t stream, const float* even, const float* odd, uint32_t width, uint32_t height, void* scratch) {
     const float4* const e4 = reinterpret_cast<const float4*>(even);
     const float4* const o4 = reinterpret_cast<const float4*>(odd);

@@ -22,6 +22,7 @@
 #undef TR_INST_EXTERN
 #include "launch_rules.h"
 #include "scene_plan.h"
+#include "denoise_plan.h"
 
 
 #ifndef WF_PIPES_MAX
@@ -978,7 +979,6 @@ int tray_render_samples_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t
     return launch_tiles(s, s->d_tiles + tile_start, w.work, w.chunk, w.chunk_stride, spp, seed, rgbw_dev, stream_, sample_begin, sample_end);
 }
 
-static bool distinct_aligned(const void* const* bufs, size_t n);
 // the ANIM argument of the debug, sampler and first-hit kernels
 static int anim_debug(const TrayDeviceScene* s) { return tr_plan::anim_debug(s->deforming, s->animated); }
 
@@ -989,7 +989,7 @@ int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32
     if (spp == 0 || (spp & (spp - 1)) != 0) { set_error("spp must be a power of two (LowDiscrepancy sampler, ld.rs:22-25); use tray_round_spp"); return TRAY_E_INVALID; }
     if (sample_begin >= sample_end || sample_end > spp) { set_error(who + ": the range must satisfy sample_begin < sample_end <= spp"); return TRAY_E_INVALID; }
     const void* const films[3] = {albedo_dev, normal_dev, depth_dev};
-    if (!distinct_aligned(films, 3u)) { set_error(who + ": the three films must be different buffers, 16-byte aligned"); return TRAY_E_INVALID; }
+    if (!tr_dnplan::distinct_aligned(films, 3u)) { set_error(who + ": the three films must be different buffers, 16-byte aligned"); return TRAY_E_INVALID; }
     if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error(who + ": sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
     if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
     tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
@@ -1013,14 +1013,14 @@ struct GuideRounds {
 };
 static uint64_t guide_scratch_bytes(uint32_t width, uint32_t height) {
     if (width == 0u || height == 0u) return 0u;
-    return tr_denoise::scratch_bytes(width, height) + (uint64_t)width * height * 32u + (uint64_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height) * 8u + 16u;
+    return tr_dnplan::plain_layout(width, height).total + (uint64_t)width * height * 32u + (uint64_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height) * 8u + 16u;
 }
 static GuideRounds guide_layout(void* scratch, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k) {
     const size_t px = (size_t)width * height, nb = (size_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height);
     GuideRounds g{};
     g.radius = radius; g.patch = patch; g.k = k;
     g.records = scratch;
-    g.fa = reinterpret_cast<float*>(static_cast<char*>(scratch) + tr_denoise::scratch_bytes(width, height));
+    g.fa = reinterpret_cast<float*>(static_cast<char*>(scratch) + tr_dnplan::plain_layout(width, height).total);
     g.fb = g.fa + 4u * px;
     g.flags = reinterpret_cast<uint32_t*>(g.fb + 4u * px);
     g.list = g.flags + nb;
@@ -1164,24 +1164,6 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
     return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, nullptr, nullptr, tile_samples, tile_error, stream_);
 }
 
-// the filter's own argument rules (tray_denoise_device's), shared by the calls that take them
-static int denoise_args(const char* who, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k) {
-    const std::string w(who);
-    if (width == 0u || height == 0u) { set_error(w + ": width and height must be >= 1"); return TRAY_E_INVALID; }
-    if (radius < 1u || radius > 10u || patch > 3u) { set_error(w + ": 1 <= radius <= 10 and patch <= 3 are required"); return TRAY_E_INVALID; }
-    if (!(k > 0.0f) || !std::isfinite(k)) { set_error(w + ": k must be > 0 and finite"); return TRAY_E_INVALID; }
-    return TRAY_OK;
-}
-// n buffers, pairwise different and 16-byte aligned
-static bool distinct_aligned(const void* const* bufs, size_t n) {
-    for (size_t i = 0; i < n; ++i) {
-        if (reinterpret_cast<uintptr_t>(bufs[i]) & 15u) return false;
-        for (size_t j = 0; j < i; ++j)
-            if (bufs[i] == bufs[j]) return false;
-    }
-    return true;
-}
-
 uint64_t tray_noise_target_filtered_scratch_bytes(uint32_t width, uint32_t height) { return guide_scratch_bytes(width, height); }
 
 int tray_render_noise_target_filtered_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
@@ -1191,463 +1173,230 @@ int tray_render_noise_target_filtered_device(TrayDeviceScene* s, uint32_t tile_s
     int rc = noise_target_args(who, s, min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
     if (rc != TRAY_OK) return rc;
     if (!scratch_dev) { set_error(std::string(who) + ": null argument"); return TRAY_E_INVALID; }
-    rc = denoise_args(who, s->dev.width, s->dev.height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
+    if (const tr_dnplan::Refusal no = tr_dnplan::filter_args(who, s->dev.width, s->dev.height, radius, patch, k); no.rc != TRAY_OK) {   // (the filter's own rules)
+        set_error(no.msg); return no.rc;
+    }
     const void* const bufs[4] = {even_dev, odd_dev, scratch_dev, out_dev};
-    if (!distinct_aligned(bufs, out_dev ? 4u : 3u)) {
+    if (!tr_dnplan::distinct_aligned(bufs, out_dev ? 4u : 3u)) {
         set_error(std::string(who) + ": the films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
     }
     const GuideRounds g = guide_layout(scratch_dev, s->dev.width, s->dev.height, radius, patch, k);
     return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, &g, out_dev, tile_samples, tile_error, stream_);
 }
 
-int tray_denoise_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
-                               const uint32_t* blocks_dev, uint32_t n_blocks, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
-    const char* const who = "tray_denoise_halves_device";
-    if (!even_dev || !odd_dev || !fa_dev || !fb_dev || !scratch_dev) { set_error(std::string(who) + ": null argument"); return TRAY_E_INVALID; }
-    const int rc = denoise_args(who, width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    const void* const bufs[5] = {even_dev, odd_dev, fa_dev, fb_dev, scratch_dev};
-    if (!distinct_aligned(bufs, 5u)) {
-        set_error(std::string(who) + ": the two films, the two outputs and the scratch buffer must be five different buffers, 16-byte aligned"); return TRAY_E_INVALID;
+// ---- the thirteen tray_denoise_*_device calls. What each refuses, its scratch layout and its launches in order are denoise_plan.h's, shared with the
+// host emulation; here the plan's schedules run with the add-on libraries' launch functions on the call's stream.
+
+namespace dn = tr_dnplan;
+static_assert(dn::kPrepareLaunches == tr_denoise::kPrepareLaunches && dn::kDenoiseLaunches == tr_denoise::kLaunches &&
+              dn::kDemodLaunches == tr_firsthit::kDemodLaunches, "the plan counts the launches of a group as its library does");
+
+struct DenoiseOps {   // the launch groups of the plan's schedules
+    hipStream_t stream;
+    uint32_t width, height;
+    void prepare(const float* even, const float* odd, void* records) { tr_denoise::prepare(stream, even, odd, width, height, records); }
+    void denoise(const float* even, const float* odd, uint32_t radius, uint32_t patch, float k, float* out, void* scratch) {
+        tr_denoise::denoise(stream, even, odd, width, height, radius, patch, k, out, scratch);
     }
-    if (blocks_dev && n_blocks > tr_guide::blocks_x(width) * tr_guide::blocks_y(height)) {
-        set_error(std::string(who) + ": the block list is longer than the frame has blocks"); return TRAY_E_INVALID;
+    void halves(const void* records, uint32_t radius, uint32_t patch, float k, const uint32_t* blocks, uint32_t n_blocks, float* fa, float* fb) {
+        tr_guide::halves(stream, records, width, height, radius, patch, k, blocks, n_blocks, fa, fb);
     }
+    void filter(const void* guide, const void* values, uint32_t radius, uint32_t patch, float k, float* out) {
+        tr_guided::filter(stream, guide, values, width, height, radius, patch, k, out);
+    }
+    void temporal_pass(const void* centre, const void* frame, uint32_t radius, uint32_t patch, float k, void* sums, bool first, bool last, float* out) {
+        tr_temporal::pass(stream, centre, frame, width, height, radius, patch, k, sums, first, last, out);
+    }
+    void tdemod_prepare(const float* even, const float* odd, const float* albedo, void* records) {
+        tr_tdemod::prepare(stream, even, odd, albedo, width, height, records);
+    }
+    void tdemod_pass(const void* centre, const void* frame, const float* albedo, uint32_t radius, uint32_t patch, float k, void* sums, bool first, bool last,
+                     float* out) {
+        tr_tdemod::pass(stream, centre, frame, albedo, width, height, radius, patch, k, sums, first, last, out);
+    }
+    void t2_halves_pass(const void* centre, const void* frame, uint32_t radius, uint32_t patch, float k, void* sums, bool first, bool last, float* fa, float* fb) {
+        tr_t2pass::halves_pass(stream, centre, frame, width, height, radius, patch, k, sums, first, last, fa, fb);
+    }
+    void t2_guided_pass(const void* centre_guide, const void* guide, const void* values, uint32_t radius, uint32_t patch, float k, void* sums, bool first,
+                        bool last, float* out) {
+        tr_t2pass::guided_pass(stream, centre_guide, guide, values, width, height, radius, patch, k, sums, first, last, out);
+    }
+    void td2_prepare(const float* even, const float* odd, const float* albedo, void* records) {
+        tr_td2pass::prepare(stream, even, odd, albedo, width, height, records);
+    }
+    void td2_guided_pass(const void* centre_guide, const void* guide, const void* values, const float* albedo, uint32_t radius, uint32_t patch, float k,
+                         void* sums, bool first, bool last, float* out) {
+        tr_td2pass::guided_pass(stream, centre_guide, guide, values, albedo, width, height, radius, patch, k, sums, first, last, out);
+    }
+    void demodulate(const float* even, const float* odd, const float* albedo, float* even_out, float* odd_out) {
+        tr_firsthit::demodulate(stream, even, odd, albedo, width, height, even_out, odd_out);
+    }
+    void remodulate(const float* albedo, float* out) { tr_firsthit::remodulate(stream, albedo, width, height, out); }
+};
+
+// a call once the plan has judged its arguments: the refusal, or the schedule on the library's current device
+extern "C++" template <class Schedule>
+static int denoise_call(const dn::Refusal& no, uint32_t width, uint32_t height, void* stream_, Schedule&& schedule) {
+    if (no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
     HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (blocks_dev && n_blocks == 0u) return TRAY_OK;   // (nothing to compute: no launch at all)
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, scratch_dev);
-    tr_guide::halves(stream, scratch_dev, width, height, radius, patch, k, blocks_dev, n_blocks, fa_dev, fb_dev);
+    DenoiseOps ops{static_cast<hipStream_t>(stream_), width, height};
+    schedule(ops);
     HIP_CHECK(hipGetLastError());
     return TRAY_OK;
 }
 
-uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height) { return tr_denoise::scratch_bytes(width, height); }
+int tray_denoise_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
+                               const uint32_t* blocks_dev, uint32_t n_blocks, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
+    const dn::Frame f{even_dev, odd_dev, nullptr, nullptr, nullptr};
+    const dn::Params p{radius, 0u, patch, k};
+    const dn::Refusal no = dn::halves_rules(width, height, f, p, blocks_dev, n_blocks, tr_guide::blocks_x(width) * tr_guide::blocks_y(height), fa_dev, fb_dev,
+                                            scratch_dev);
+    if (no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
+    HIP_CHECK(hipSetDevice(g_device));
+    if (blocks_dev && n_blocks == 0u) return TRAY_OK;   // (nothing to compute: no launch at all)
+    DenoiseOps ops{static_cast<hipStream_t>(stream_), width, height};
+    dn::halves(ops, f, p, blocks_dev, n_blocks, fa_dev, fb_dev, scratch_dev);
+    HIP_CHECK(hipGetLastError());
+    return TRAY_OK;
+}
+
+uint64_t tray_denoise_scratch_bytes(uint32_t width, uint32_t height) { return dn::plain_layout(width, height).total; }
 
 int tray_denoise_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                         float* out_dev, void* scratch_dev, void* stream_) {
-    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error("tray_denoise_device: null argument"); return TRAY_E_INVALID; }
-    const int rc = denoise_args("tray_denoise_device", width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (even_dev == odd_dev || out_dev == even_dev || out_dev == odd_dev) {
-        set_error("tray_denoise_device: the two films and the output must be three different buffers"); return TRAY_E_INVALID;
-    }
-    if ((reinterpret_cast<uintptr_t>(even_dev) | reinterpret_cast<uintptr_t>(odd_dev) | reinterpret_cast<uintptr_t>(out_dev) |
-         reinterpret_cast<uintptr_t>(scratch_dev)) & 15u) {
-        set_error("tray_denoise_device: the films, the output and the scratch buffer must be 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    tr_denoise::denoise(static_cast<hipStream_t>(stream_), even_dev, odd_dev, width, height, radius, patch, k, out_dev, scratch_dev);
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, nullptr, nullptr};
+    const dn::Params p{radius, 0u, patch, k};
+    return denoise_call(dn::denoise_rules(width, height, even_dev, odd_dev, p, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::denoise(ops, f, p, out_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_temporal_scratch_bytes(uint32_t width, uint32_t height) { return tr_temporal::scratch_bytes(width, height); }
+uint64_t tray_denoise_temporal_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_layout(width, height).total; }
 
 int tray_denoise_temporal_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
                                  const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
                                  float* out_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_temporal_device");
-    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (radius_t < 1u || radius_t > radius) { set_error(who + ": 1 <= radius_t <= radius is required"); return TRAY_E_INVALID; }
-    if (n_neighbours > TRAY_DENOISE_MAX_NEIGHBOURS) {
-        set_error(who + ": at most " + std::to_string(TRAY_DENOISE_MAX_NEIGHBOURS) + " neighbouring frames"); return TRAY_E_INVALID;
-    }
-    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const void* bufs[2u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 2u] = {even_dev, odd_dev, out_dev, scratch_dev};
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        if (!nb_even_dev[j] || !nb_odd_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
-        bufs[4u + 2u * j] = nb_even_dev[j];
-        bufs[5u + 2u * j] = nb_odd_dev[j];
-    }
-    if (!distinct_aligned(bufs, 4u + 2u * n_neighbours)) {
-        set_error(who + ": every frame's two films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_temporal::Layout l = tr_temporal::layout(scratch_dev, width, height);
-    // the centre's window first, then every neighbour's in the caller's order: each frame is prepare's two launches and one pass
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.centre);
-    tr_temporal::pass(stream, l.centre, l.centre, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, out_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
-        tr_temporal::pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, nullptr, nullptr};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nullptr, nullptr, nullptr};
+    const dn::Params p{radius, radius_t, patch, k};
+    return denoise_call(dn::temporal_rules(width, height, f, nb, p, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal(ops, f, nb, p, out_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_guided_scratch_bytes(uint32_t width, uint32_t height) { return tr_guided::scratch_bytes(width, height); }
+uint64_t tray_denoise_guided_scratch_bytes(uint32_t width, uint32_t height) { return dn::guided_layout(width, height).total; }
 
 int tray_denoise_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* guide_a_dev, const float* guide_b_dev,
                                uint32_t radius, uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_guided_device");
-    if (!even_dev || !odd_dev || !guide_a_dev || !guide_b_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    // (the guide may be the films themselves: then the call is tray_denoise_device)
-    const void* const inputs[4] = {even_dev, odd_dev, guide_a_dev, guide_b_dev};
-    bool ok = even_dev != odd_dev && guide_a_dev != guide_b_dev && out_dev != scratch_dev &&
-              ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(scratch_dev)) & 15u) == 0u;
-    for (const void* in : inputs) ok = ok && (reinterpret_cast<uintptr_t>(in) & 15u) == 0u && in != out_dev && in != scratch_dev;
-    if (!ok) {
-        set_error(who + ": the two films must differ, the two guide films must differ, the output and the scratch buffer must differ from all four "
-                        "and from each other, and all six must be 16-byte aligned");
-        return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_guided::Layout l = tr_guided::layout(scratch_dev, width, height);
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
-    tr_denoise::prepare(stream, guide_a_dev, guide_b_dev, width, height, l.guide);
-    tr_guided::filter(stream, l.guide, l.values, width, height, radius, patch, k, out_dev);
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, guide_a_dev, guide_b_dev};
+    const dn::Params p{radius, 0u, patch, k};
+    return denoise_call(dn::guided_rules(width, height, f, p, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::guided(ops, f, p, out_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return tr_guided::two_pass_scratch_bytes(width, height); }
-
-// the six launches of a two-pass call: the first pass as tray_denoise_halves_device over every block -- its records of the films are the second
-// pass's values --, then the guided filter with the pilot as guide
-static void two_pass_launches(hipStream_t stream, uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch,
-                              float k, uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev) {
-    const tr_guided::TwoPassLayout l = tr_guided::two_pass_layout(scratch_dev, width, height);
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
-    tr_guide::halves(stream, l.values, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
-    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
-    tr_guided::filter(stream, l.guide, l.values, width, height, radius2, patch2, k2, out_dev);
-}
+uint64_t tray_denoise_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return dn::two_pass_layout(width, height).total; }
 
 int tray_denoise_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t radius, uint32_t patch, float k,
                                  uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_two_pass_device");
-    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    rc = denoise_args((who + ", second pass").c_str(), width, height, radius2, patch2, k2);
-    if (rc != TRAY_OK) return rc;
-    const void* const bufs[4] = {even_dev, odd_dev, out_dev, scratch_dev};
-    if (!distinct_aligned(bufs, 4u)) {
-        set_error(who + ": the two films, the output and the scratch buffer must be four different buffers, 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    two_pass_launches(static_cast<hipStream_t>(stream_), width, height, even_dev, odd_dev, radius, patch, k, radius2, patch2, k2, out_dev, scratch_dev);
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, nullptr, nullptr};
+    const dn::Params p{radius, 0u, patch, k}, second{radius2, 0u, patch2, k2};
+    return denoise_call(dn::two_pass_rules(width, height, f, p, second, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::two_pass(ops, f, p, second, out_dev, scratch_dev); });
 }
 
 uint64_t tray_denoise_demodulated_scratch_bytes(uint32_t width, uint32_t height, uint32_t radius2) {
-    if (width == 0u || height == 0u) return 0u;
-    return (radius2 ? tr_guided::two_pass_scratch_bytes(width, height) : tr_denoise::scratch_bytes(width, height)) + tr_firsthit::demod_bytes(width, height);
+    return dn::demodulated_layout(width, height, radius2 != 0u).total;
 }
 
 int tray_denoise_demodulated_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev, uint32_t radius,
                                     uint32_t patch, float k, uint32_t radius2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_demodulated_device");
-    if (!even_dev || !odd_dev || !albedo_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (radius2 != 0u) {
-        rc = denoise_args((who + ", second pass").c_str(), width, height, radius2, patch2, k2);
-        if (rc != TRAY_OK) return rc;
-    }
-    const void* const bufs[5] = {even_dev, odd_dev, albedo_dev, out_dev, scratch_dev};
-    if (!distinct_aligned(bufs, 5u)) {
-        set_error(who + ": the two films, the albedo film, the output and the scratch buffer must be five different buffers, 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // [the filter's scratch | E' | O']
-    const size_t film = (size_t)width * height * 16u;
-    char* const after = static_cast<char*>(scratch_dev) + (radius2 ? tr_guided::two_pass_scratch_bytes(width, height) : tr_denoise::scratch_bytes(width, height));
-    float* const e = reinterpret_cast<float*>(after);
-    float* const o = reinterpret_cast<float*>(after + film);
-    tr_firsthit::demodulate(stream, even_dev, odd_dev, albedo_dev, width, height, e, o);
-    if (radius2) two_pass_launches(stream, width, height, e, o, radius, patch, k, radius2, patch2, k2, out_dev, scratch_dev);
-    else tr_denoise::denoise(stream, e, o, width, height, radius, patch, k, out_dev, scratch_dev);
-    tr_firsthit::remodulate(stream, albedo_dev, width, height, out_dev);
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, albedo_dev, nullptr, nullptr};
+    const dn::Params p{radius, 0u, patch, k}, second_pass{radius2, 0u, patch2, k2};
+    const dn::Params* const second = radius2 != 0u ? &second_pass : nullptr;   // (radius2 == 0: one pass)
+    return denoise_call(dn::demodulated_rules(width, height, f, p, second, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::demodulated(ops, f, p, second, out_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_temporal_demodulated_scratch_bytes(uint32_t width, uint32_t height) { return tr_tdemod::scratch_bytes(width, height); }
+uint64_t tray_denoise_temporal_demodulated_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_layout(width, height).total; }
 
 int tray_denoise_temporal_demodulated_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
                                              uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
                                              const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k, float* out_dev,
                                              void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_temporal_demodulated_device");
-    if (!even_dev || !odd_dev || !albedo_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (radius_t < 1u || radius_t > radius) { set_error(who + ": 1 <= radius_t <= radius is required"); return TRAY_E_INVALID; }
-    if (n_neighbours > TRAY_DENOISE_MAX_NEIGHBOURS) {
-        set_error(who + ": at most " + std::to_string(TRAY_DENOISE_MAX_NEIGHBOURS) + " neighbouring frames"); return TRAY_E_INVALID;
-    }
-    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev || !nb_albedo_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const void* bufs[3u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 2u] = {even_dev, odd_dev, albedo_dev, out_dev, scratch_dev};
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        if (!nb_even_dev[j] || !nb_odd_dev[j] || !nb_albedo_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
-        bufs[5u + 3u * j] = nb_even_dev[j];
-        bufs[6u + 3u * j] = nb_odd_dev[j];
-        bufs[7u + 3u * j] = nb_albedo_dev[j];
-    }
-    if (!distinct_aligned(bufs, 5u + 3u * n_neighbours)) {
-        set_error(who + ": every frame's two films and albedo film, the output and the scratch buffer must be different buffers, 16-byte aligned");
-        return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_tdemod::Layout l = tr_tdemod::layout(scratch_dev, width, height);
-    // as tray_denoise_temporal_device: per frame two preparing launches and one pass; the centre's albedo scales the last pass's output
-    tr_tdemod::prepare(stream, even_dev, odd_dev, albedo_dev, width, height, l.centre);
-    tr_tdemod::pass(stream, l.centre, l.centre, albedo_dev, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, out_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_tdemod::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
-        tr_tdemod::pass(stream, l.centre, l.neighbour, albedo_dev, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, albedo_dev, nullptr, nullptr};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nb_albedo_dev, nullptr, nullptr};
+    const dn::Params p{radius, radius_t, patch, k};
+    return denoise_call(dn::temporal_demodulated_rules(width, height, f, nb, p, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_demodulated(ops, f, nb, p, out_dev, scratch_dev); });
 }
 
-// ---- the second pass over all frames (t2pass.h): tray_denoise_temporal_halves_device, _guided_device, _two_pass_device
-
-// the temporal calls' rules for (radius, radius_t, patch, k) and for N
-static int temporal_args(const std::string& who, uint32_t width, uint32_t height, uint32_t n_neighbours, uint32_t radius, uint32_t radius_t, uint32_t patch,
-                         float k) {
-    const int rc = denoise_args(who.c_str(), width, height, radius, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (radius_t < 1u || radius_t > radius) { set_error(who + ": 1 <= radius_t <= radius is required"); return TRAY_E_INVALID; }
-    if (n_neighbours > TRAY_DENOISE_MAX_NEIGHBOURS) {
-        set_error(who + ": at most " + std::to_string(TRAY_DENOISE_MAX_NEIGHBOURS) + " neighbouring frames"); return TRAY_E_INVALID;
-    }
-    return TRAY_OK;
-}
-
-uint64_t tray_denoise_temporal_halves_scratch_bytes(uint32_t width, uint32_t height) { return tr_t2pass::halves_scratch_bytes(width, height); }
-
-// the 3 (N + 1) launches of the pilot over all frames into (fa, fb): l's three regions are the temporal call's
-static void temporal_halves_launches(hipStream_t stream, uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
-                                     const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
-                                     float* fa_dev, float* fb_dev, const tr_t2pass::HalvesLayout& l) {
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.centre);
-    tr_t2pass::halves_pass(stream, l.centre, l.centre, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, fa_dev, fb_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
-        tr_t2pass::halves_pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, fa_dev, fb_dev);
-    }
-}
+uint64_t tray_denoise_temporal_halves_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_layout(width, height).total; }
 
 int tray_denoise_temporal_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
                                         const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch,
                                         float k, float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_temporal_halves_device");
-    if (!even_dev || !odd_dev || !fa_dev || !fb_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const void* bufs[2u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 3u] = {even_dev, odd_dev, fa_dev, fb_dev, scratch_dev};
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        if (!nb_even_dev[j] || !nb_odd_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
-        bufs[5u + 2u * j] = nb_even_dev[j];
-        bufs[6u + 2u * j] = nb_odd_dev[j];
-    }
-    if (!distinct_aligned(bufs, 5u + 2u * n_neighbours)) {
-        set_error(who + ": every frame's two films, the two outputs and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    temporal_halves_launches(static_cast<hipStream_t>(stream_), width, height, even_dev, odd_dev, n_neighbours, nb_even_dev, nb_odd_dev, radius, radius_t, patch, k,
-                             fa_dev, fb_dev, tr_t2pass::halves_layout(scratch_dev, width, height));
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, nullptr, nullptr};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nullptr, nullptr, nullptr};
+    const dn::Params p{radius, radius_t, patch, k};
+    return denoise_call(dn::temporal_halves_rules(width, height, f, nb, p, fa_dev, fb_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_halves(ops, f, nb, p, fa_dev, fb_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_temporal_guided_scratch_bytes(uint32_t width, uint32_t height) { return tr_t2pass::guided_scratch_bytes(width, height); }
+uint64_t tray_denoise_temporal_guided_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_guided_layout(width, height).total; }
 
 int tray_denoise_temporal_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* guide_a_dev,
                                         const float* guide_b_dev, uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
                                         const float* const* nb_guide_a_dev, const float* const* nb_guide_b_dev, uint32_t radius, uint32_t radius_t,
                                         uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_temporal_guided_device");
-    if (!even_dev || !odd_dev || !guide_a_dev || !guide_b_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
-    if (rc != TRAY_OK) return rc;
-    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev || !nb_guide_a_dev || !nb_guide_b_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    for (uint32_t j = 0; j < n_neighbours; ++j)
-        if (!nb_even_dev[j] || !nb_odd_dev[j] || !nb_guide_a_dev[j] || !nb_guide_b_dev[j]) {
-            set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID;
-        }
-    // the inputs are only read: a frame's guide may be its own films (then the call is tray_denoise_temporal_device); the two films of a pair
-    // differ, and the output and the scratch buffer differ from every film and from each other
-    bool ok = out_dev != scratch_dev && ((reinterpret_cast<uintptr_t>(out_dev) | reinterpret_cast<uintptr_t>(scratch_dev)) & 15u) == 0u;
-    for (uint32_t j = 0; j <= n_neighbours; ++j) {
-        const void* const in[4] = {j ? nb_even_dev[j - 1u] : even_dev, j ? nb_odd_dev[j - 1u] : odd_dev, j ? nb_guide_a_dev[j - 1u] : guide_a_dev,
-                                   j ? nb_guide_b_dev[j - 1u] : guide_b_dev};
-        ok = ok && in[0] != in[1] && in[2] != in[3];
-        for (const void* f : in) ok = ok && (reinterpret_cast<uintptr_t>(f) & 15u) == 0u && f != out_dev && f != scratch_dev;
-    }
-    if (!ok) {
-        set_error(who + ": a frame's two films must differ, its two guide films must differ, the output and the scratch buffer must differ from every "
-                        "film and from each other, and all must be 16-byte aligned");
-        return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_t2pass::GuidedLayout l = tr_t2pass::guided_layout(scratch_dev, width, height);
-    // the centre's window first, then every neighbour's in the caller's order: per frame prepare of the values, prepare of the guide, one pass
-    tr_denoise::prepare(stream, even_dev, odd_dev, width, height, l.values);
-    tr_denoise::prepare(stream, guide_a_dev, guide_b_dev, width, height, l.centre_guide);
-    tr_t2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.values, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, out_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.values);
-        tr_denoise::prepare(stream, nb_guide_a_dev[j], nb_guide_b_dev[j], width, height, l.guide);
-        tr_t2pass::guided_pass(stream, l.centre_guide, l.guide, l.values, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, out_dev);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, guide_a_dev, guide_b_dev};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nullptr, nb_guide_a_dev, nb_guide_b_dev};
+    const dn::Params p{radius, radius_t, patch, k};
+    return denoise_call(dn::temporal_guided_rules(width, height, f, nb, p, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_guided(ops, f, nb, p, out_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_temporal_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return tr_t2pass::two_pass_scratch_bytes(width, height); }
+uint64_t tray_denoise_temporal_two_pass_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_two_pass_layout(width, height).total; }
 
 int tray_denoise_temporal_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, uint32_t n_neighbours,
                                           const float* const* nb_even_dev, const float* const* nb_odd_dev, uint32_t radius, uint32_t radius_t, uint32_t patch,
                                           float k, uint32_t radius2, uint32_t radius_t2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev,
                                           void* stream_) {
-    const std::string who("tray_denoise_temporal_two_pass_device");
-    if (!even_dev || !odd_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
-    if (rc != TRAY_OK) return rc;
-    rc = temporal_args(who + ", second pass", width, height, n_neighbours, radius2, radius_t2, patch2, k2);
-    if (rc != TRAY_OK) return rc;
-    if (n_neighbours > 0u && (!nb_even_dev || !nb_odd_dev)) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    const void* bufs[2u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 2u] = {even_dev, odd_dev, out_dev, scratch_dev};
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        if (!nb_even_dev[j] || !nb_odd_dev[j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
-        bufs[4u + 2u * j] = nb_even_dev[j];
-        bufs[5u + 2u * j] = nb_odd_dev[j];
-    }
-    if (!distinct_aligned(bufs, 4u + 2u * n_neighbours)) {
-        set_error(who + ": every frame's two films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_t2pass::TwoPassLayout l = tr_t2pass::two_pass_layout(scratch_dev, width, height);
-    // first pass: the centre's pilot over all frames (l.centre keeps the centre's records: the second pass's values of frame 0)
-    temporal_halves_launches(stream, width, height, even_dev, odd_dev, n_neighbours, nb_even_dev, nb_odd_dev, radius, radius_t, patch, k, l.fa, l.fb,
-                             tr_t2pass::HalvesLayout{l.centre, l.neighbour, l.sums});
-    // second pass: the centre guided by that pilot, then every neighbour guided by its own single-frame pilot, one at a time -- its records are
-    // resolved again (the first pass's are overwritten by the next neighbour's), and (fa, fb) is free once the pilot before it is resolved
-    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.centre_guide);
-    tr_t2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.centre, width, height, radius2, patch2, k2, l.sums, true, n_neighbours == 0u, out_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_denoise::prepare(stream, nb_even_dev[j], nb_odd_dev[j], width, height, l.neighbour);
-        tr_guide::halves(stream, l.neighbour, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
-        tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
-        tr_t2pass::guided_pass(stream, l.centre_guide, l.guide, l.neighbour, width, height, radius_t2, patch2, k2, l.sums, false, j + 1u == n_neighbours, out_dev);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, nullptr, nullptr, nullptr};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nullptr, nullptr, nullptr};
+    const dn::Params p{radius, radius_t, patch, k}, second{radius2, radius_t2, patch2, k2};
+    return denoise_call(dn::temporal_two_pass_rules(width, height, f, nb, p, second, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_two_pass(ops, f, nb, p, second, out_dev, scratch_dev); });
 }
 
-// ---- the two-pass temporal filter on albedo-demodulated films (td2pass.h): tray_denoise_temporal_demodulated_halves_device, _guided_device,
-// _two_pass_device
+// the two-pass temporal filter on albedo-demodulated films: the three calls above with every frame's films resolved through its albedo
 
-// what the three calls refuse about their buffers: `fixed` holds the centre's films, the outputs and the scratch buffer (n_fixed of them, none
-// null), `nb` the n_arrays host arrays of the neighbours' films; all are pairwise different and 16-byte aligned
-static int demodulated_buffers(const std::string& who, const void* const* fixed, uint32_t n_fixed, const float* const* const* nb, uint32_t n_arrays,
-                               uint32_t n_neighbours) {
-    const void* bufs[5u * (TRAY_DENOISE_MAX_NEIGHBOURS + 1u) + 3u];
-    uint32_t n = 0;
-    for (uint32_t i = 0; i < n_fixed; ++i) bufs[n++] = fixed[i];
-    for (uint32_t a = 0; a < n_arrays; ++a)
-        if (n_neighbours > 0u && !nb[a]) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    for (uint32_t j = 0; j < n_neighbours; ++j)
-        for (uint32_t a = 0; a < n_arrays; ++a) {
-            if (!nb[a][j]) { set_error(who + ": null film of a neighbouring frame"); return TRAY_E_INVALID; }
-            bufs[n++] = nb[a][j];
-        }
-    if (!distinct_aligned(bufs, n)) {
-        set_error(who + ": every frame's films and albedo film, the outputs and the scratch buffer must be different buffers, 16-byte aligned");
-        return TRAY_E_INVALID;
-    }
-    return TRAY_OK;
-}
-
-uint64_t tray_denoise_temporal_demodulated_halves_scratch_bytes(uint32_t width, uint32_t height) { return tr_td2pass::halves_scratch_bytes(width, height); }
-
-// the 3 (N + 1) launches of the pilot over all frames' demodulated films into (fa, fb): temporal_halves_launches with tr_td2pass::prepare
-static void demodulated_halves_launches(hipStream_t stream, uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
-                                        uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
-                                        const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k, float* fa_dev,
-                                        float* fb_dev, const tr_t2pass::HalvesLayout& l) {
-    tr_td2pass::prepare(stream, even_dev, odd_dev, albedo_dev, width, height, l.centre);
-    tr_t2pass::halves_pass(stream, l.centre, l.centre, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u, fa_dev, fb_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_td2pass::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
-        tr_t2pass::halves_pass(stream, l.centre, l.neighbour, width, height, radius_t, patch, k, l.sums, false, j + 1u == n_neighbours, fa_dev, fb_dev);
-    }
-}
+uint64_t tray_denoise_temporal_demodulated_halves_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_layout(width, height).total; }
 
 int tray_denoise_temporal_demodulated_halves_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
                                                     uint32_t n_neighbours, const float* const* nb_even_dev, const float* const* nb_odd_dev,
                                                     const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
                                                     float* fa_dev, float* fb_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_temporal_demodulated_halves_device");
-    if (!even_dev || !odd_dev || !albedo_dev || !fa_dev || !fb_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
-    if (rc != TRAY_OK) return rc;
-    const void* const fixed[6] = {even_dev, odd_dev, albedo_dev, fa_dev, fb_dev, scratch_dev};
-    const float* const* const nb[3] = {nb_even_dev, nb_odd_dev, nb_albedo_dev};
-    rc = demodulated_buffers(who, fixed, 6u, nb, 3u, n_neighbours);
-    if (rc != TRAY_OK) return rc;
-    HIP_CHECK(hipSetDevice(g_device));
-    demodulated_halves_launches(static_cast<hipStream_t>(stream_), width, height, even_dev, odd_dev, albedo_dev, n_neighbours, nb_even_dev, nb_odd_dev,
-                                nb_albedo_dev, radius, radius_t, patch, k, fa_dev, fb_dev, tr_t2pass::halves_layout(scratch_dev, width, height));
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, albedo_dev, nullptr, nullptr};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nb_albedo_dev, nullptr, nullptr};
+    const dn::Params p{radius, radius_t, patch, k};
+    return denoise_call(dn::temporal_demodulated_halves_rules(width, height, f, nb, p, fa_dev, fb_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_demodulated_halves(ops, f, nb, p, fa_dev, fb_dev, scratch_dev); });
 }
 
-uint64_t tray_denoise_temporal_demodulated_guided_scratch_bytes(uint32_t width, uint32_t height) { return tr_td2pass::guided_scratch_bytes(width, height); }
+uint64_t tray_denoise_temporal_demodulated_guided_scratch_bytes(uint32_t width, uint32_t height) { return dn::temporal_guided_layout(width, height).total; }
 
 int tray_denoise_temporal_demodulated_guided_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
                                                     const float* guide_a_dev, const float* guide_b_dev, uint32_t n_neighbours,
                                                     const float* const* nb_even_dev, const float* const* nb_odd_dev, const float* const* nb_albedo_dev,
                                                     const float* const* nb_guide_a_dev, const float* const* nb_guide_b_dev, uint32_t radius,
                                                     uint32_t radius_t, uint32_t patch, float k, float* out_dev, void* scratch_dev, void* stream_) {
-    const std::string who("tray_denoise_temporal_demodulated_guided_device");
-    if (!even_dev || !odd_dev || !albedo_dev || !guide_a_dev || !guide_b_dev || !out_dev || !scratch_dev) {
-        set_error(who + ": null argument"); return TRAY_E_INVALID;
-    }
-    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
-    if (rc != TRAY_OK) return rc;
-    const void* const fixed[7] = {even_dev, odd_dev, albedo_dev, guide_a_dev, guide_b_dev, out_dev, scratch_dev};
-    const float* const* const nb[5] = {nb_even_dev, nb_odd_dev, nb_albedo_dev, nb_guide_a_dev, nb_guide_b_dev};
-    rc = demodulated_buffers(who, fixed, 7u, nb, 5u, n_neighbours);
-    if (rc != TRAY_OK) return rc;
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_t2pass::GuidedLayout l = tr_t2pass::guided_layout(scratch_dev, width, height);
-    // as tray_denoise_temporal_guided_device: per frame prepare of the (demodulated) values, prepare of the guide, one pass; the centre's albedo
-    // scales the last pass's output
-    tr_td2pass::prepare(stream, even_dev, odd_dev, albedo_dev, width, height, l.values);
-    tr_denoise::prepare(stream, guide_a_dev, guide_b_dev, width, height, l.centre_guide);
-    tr_td2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.values, albedo_dev, width, height, radius, patch, k, l.sums, true, n_neighbours == 0u,
-                            out_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_td2pass::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.values);
-        tr_denoise::prepare(stream, nb_guide_a_dev[j], nb_guide_b_dev[j], width, height, l.guide);
-        tr_td2pass::guided_pass(stream, l.centre_guide, l.guide, l.values, albedo_dev, width, height, radius_t, patch, k, l.sums, false,
-                                j + 1u == n_neighbours, out_dev);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, albedo_dev, guide_a_dev, guide_b_dev};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nb_albedo_dev, nb_guide_a_dev, nb_guide_b_dev};
+    const dn::Params p{radius, radius_t, patch, k};
+    return denoise_call(dn::temporal_demodulated_guided_rules(width, height, f, nb, p, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_demodulated_guided(ops, f, nb, p, out_dev, scratch_dev); });
 }
 
 uint64_t tray_denoise_temporal_demodulated_two_pass_scratch_bytes(uint32_t width, uint32_t height) {
-    return tr_td2pass::two_pass_scratch_bytes(width, height);
+    return dn::temporal_two_pass_layout(width, height).total;
 }
 
 int tray_denoise_temporal_demodulated_two_pass_device(uint32_t width, uint32_t height, const float* even_dev, const float* odd_dev, const float* albedo_dev,
@@ -1655,37 +1404,13 @@ int tray_denoise_temporal_demodulated_two_pass_device(uint32_t width, uint32_t h
                                                       const float* const* nb_albedo_dev, uint32_t radius, uint32_t radius_t, uint32_t patch, float k,
                                                       uint32_t radius2, uint32_t radius_t2, uint32_t patch2, float k2, float* out_dev, void* scratch_dev,
                                                       void* stream_) {
-    const std::string who("tray_denoise_temporal_demodulated_two_pass_device");
-    if (!even_dev || !odd_dev || !albedo_dev || !out_dev || !scratch_dev) { set_error(who + ": null argument"); return TRAY_E_INVALID; }
-    int rc = temporal_args(who, width, height, n_neighbours, radius, radius_t, patch, k);
-    if (rc != TRAY_OK) return rc;
-    rc = temporal_args(who + ", second pass", width, height, n_neighbours, radius2, radius_t2, patch2, k2);
-    if (rc != TRAY_OK) return rc;
-    const void* const fixed[5] = {even_dev, odd_dev, albedo_dev, out_dev, scratch_dev};
-    const float* const* const nb[3] = {nb_even_dev, nb_odd_dev, nb_albedo_dev};
-    rc = demodulated_buffers(who, fixed, 5u, nb, 3u, n_neighbours);
-    if (rc != TRAY_OK) return rc;
-    HIP_CHECK(hipSetDevice(g_device));
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const tr_t2pass::TwoPassLayout l = tr_t2pass::two_pass_layout(scratch_dev, width, height);
-    static_assert(tr_td2pass::two_pass_launches(2u) == 9u * 2u + 6u, "9 N + 6 launches: the two-pass temporal call's");
-    // tray_denoise_temporal_two_pass_device's launches, one for one: every frame's films are resolved through their albedo (tr_td2pass::prepare),
-    // the pilots -- demodulated films already -- as they are, and the last guided pass multiplies the centre's scale back in
-    demodulated_halves_launches(stream, width, height, even_dev, odd_dev, albedo_dev, n_neighbours, nb_even_dev, nb_odd_dev, nb_albedo_dev, radius, radius_t,
-                                patch, k, l.fa, l.fb, tr_t2pass::HalvesLayout{l.centre, l.neighbour, l.sums});
-    tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.centre_guide);
-    tr_td2pass::guided_pass(stream, l.centre_guide, l.centre_guide, l.centre, albedo_dev, width, height, radius2, patch2, k2, l.sums, true, n_neighbours == 0u,
-                            out_dev);
-    for (uint32_t j = 0; j < n_neighbours; ++j) {
-        tr_td2pass::prepare(stream, nb_even_dev[j], nb_odd_dev[j], nb_albedo_dev[j], width, height, l.neighbour);
-        tr_guide::halves(stream, l.neighbour, width, height, radius, patch, k, nullptr, 0u, l.fa, l.fb);
-        tr_denoise::prepare(stream, l.fa, l.fb, width, height, l.guide);
-        tr_td2pass::guided_pass(stream, l.centre_guide, l.guide, l.neighbour, albedo_dev, width, height, radius_t2, patch2, k2, l.sums, false,
-                                j + 1u == n_neighbours, out_dev);
-    }
-    HIP_CHECK(hipGetLastError());
-    return TRAY_OK;
+    const dn::Frame f{even_dev, odd_dev, albedo_dev, nullptr, nullptr};
+    const dn::Neighbours nb{n_neighbours, nb_even_dev, nb_odd_dev, nb_albedo_dev, nullptr, nullptr};
+    const dn::Params p{radius, radius_t, patch, k}, second{radius2, radius_t2, patch2, k2};
+    return denoise_call(dn::temporal_demodulated_two_pass_rules(width, height, f, nb, p, second, out_dev, scratch_dev), width, height, stream_,
+                        [&](DenoiseOps& ops) { dn::temporal_demodulated_two_pass(ops, f, nb, p, second, out_dev, scratch_dev); });
 }
+
 
 int tray_multi_shard_samples(uint32_t spp, uint32_t d, uint32_t n_dev, uint32_t* begin, uint32_t* end) {
     if (!begin || !end) { set_error("tray_multi_shard_samples: null argument"); return TRAY_E_INVALID; }

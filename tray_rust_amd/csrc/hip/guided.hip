@@ -8,21 +8,6 @@
 
 namespace tr_guided {
 
-uint64_t scratch_bytes(uint32_t width, uint32_t height) { return gdn_scratch_bytes(width, height); }
-
-Layout layout(void* scratch, uint32_t width, uint32_t height) {
-    char* const base = static_cast<char*>(scratch);
-    return {base, base + (size_t)dn_scratch_bytes(width, height)};
-}
-
-uint64_t two_pass_scratch_bytes(uint32_t width, uint32_t height) { return gdn_two_pass_scratch_bytes(width, height); }
-
-TwoPassLayout two_pass_layout(void* scratch, uint32_t width, uint32_t height) {
-    const size_t records = (size_t)dn_scratch_bytes(width, height), film = (size_t)width * height * 16u;
-    char* const base = static_cast<char*>(scratch);
-    return {base, reinterpret_cast<float*>(base + records), reinterpret_cast<float*>(base + records + film), base + records + 2u * film};
-}
-
 void filter(hipStream_t stream, const void* guide_records, const void* value_records, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k,
             float* out) {
     const float4* const g4 = static_cast<const float4*>(guide_records);

@@ -9,30 +9,6 @@
 
 namespace tr_t2pass {
 
-uint64_t halves_scratch_bytes(uint32_t width, uint32_t height) { return t2p_halves_scratch_bytes(width, height); }
-uint64_t guided_scratch_bytes(uint32_t width, uint32_t height) { return t2p_guided_scratch_bytes(width, height); }
-uint64_t two_pass_scratch_bytes(uint32_t width, uint32_t height) { return t2p_two_pass_scratch_bytes(width, height); }
-
-HalvesLayout halves_layout(void* scratch, uint32_t width, uint32_t height) {
-    const size_t records = (size_t)dn_scratch_bytes(width, height);
-    char* const base = static_cast<char*>(scratch);
-    return {base, base + records, base + 2u * records};
-}
-
-GuidedLayout guided_layout(void* scratch, uint32_t width, uint32_t height) {
-    const size_t records = (size_t)dn_scratch_bytes(width, height);
-    char* const base = static_cast<char*>(scratch);
-    return {base, base + records, base + 2u * records, base + 3u * records};
-}
-
-TwoPassLayout two_pass_layout(void* scratch, uint32_t width, uint32_t height) {
-    const size_t records = (size_t)dn_scratch_bytes(width, height), film = (size_t)width * height * 16u;
-    char* const base = static_cast<char*>(scratch);
-    char* const pilot = base + 2u * records + 2u * film;
-    return {base, base + records, base + 2u * records, reinterpret_cast<float*>(pilot), reinterpret_cast<float*>(pilot + film), pilot + 2u * film,
-            pilot + 2u * film + records};
-}
-
 void halves_pass(hipStream_t stream, const void* centre_records, const void* frame_records, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch,
                  float k, void* sums, bool first, bool last, float* fa, float* fb) {
     const float4* const c4 = static_cast<const float4*>(centre_records);

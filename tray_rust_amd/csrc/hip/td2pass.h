@@ -2,18 +2,10 @@
 // (include/trayhip.h): k_td2_guided_pass and instances of k_tdm_prepare and k_dn_prepare<1> (td2pass_kernels.h) live in libtrayhip_td2pass.so,
 // compiled from td2pass.hip; device_api.hip launches them through these functions, between tr_denoise::prepare's, tr_guide::halves' and
 // tr_t2pass::halves_pass' launches (denoise.h, guide.h, t2pass.h), so that libtrayhip.so's and every other add-on library's code objects stay
-// what they were.
+// what they were. The three calls' schedules, launch counts and scratch layouts -- the two-pass temporal calls' -- are denoise_plan.h's.
 #pragma once
-#include "t2pass.h"
 
 namespace tr_td2pass {
-// launches and bytes of scratch of the three calls with N neighbours: the two-pass temporal calls', whose layouts (tr_t2pass::*_layout) they use
-constexpr uint32_t halves_launches(uint32_t n) { return tr_t2pass::halves_launches(n); }
-constexpr uint32_t guided_launches(uint32_t n) { return tr_t2pass::guided_launches(n); }
-constexpr uint32_t two_pass_launches(uint32_t n) { return tr_t2pass::two_pass_launches(n); }
-uint64_t halves_scratch_bytes(uint32_t width, uint32_t height);     // 128 per pixel
-uint64_t guided_scratch_bytes(uint32_t width, uint32_t height);     // 176 per pixel
-uint64_t two_pass_scratch_bytes(uint32_t width, uint32_t height);   // 256 per pixel
 // the two preparing launches of one frame's values: k_tdm_prepare (the records of the films divided by the scale of `albedo`), then k_dn_prepare<1>
 void prepare(hipStream_t stream, const float* even, const float* odd, const float* albedo, uint32_t width, uint32_t height, void* records);
 // one k_td2_guided_pass<patch> over all 32 x 16 tiles, as tr_t2pass::guided_pass; last: the normalised image times the scale of `albedo` (the

@@ -9,10 +9,6 @@
 
 namespace tr_td2pass {
 
-uint64_t halves_scratch_bytes(uint32_t width, uint32_t height) { return td2_halves_scratch_bytes(width, height); }
-uint64_t guided_scratch_bytes(uint32_t width, uint32_t height) { return td2_guided_scratch_bytes(width, height); }
-uint64_t two_pass_scratch_bytes(uint32_t width, uint32_t height) { return td2_two_pass_scratch_bytes(width, height); }
-
 void prepare(hipStream_t stream, const float* even, const float* odd, const float* albedo, uint32_t width, uint32_t height, void* records) {
     const float4* const e4 = reinterpret_cast<const float4*>(even);
     const float4* const o4 = reinterpret_cast<const float4*>(odd);

@@ -1,14 +1,10 @@
 // The albedo-demodulated temporal filter of tray_denoise_temporal_demodulated_device (include/trayhip.h): k_tdm_prepare, k_tdm_pass and an instance
 // of k_dn_prepare<1> (tdemod_kernels.h) live in libtrayhip_tdemod.so, compiled from tdemod.hip; device_api.hip launches them through these
-// functions, so that libtrayhip.so's and every other add-on library's code objects stay what they were.
+// functions, so that libtrayhip.so's and every other add-on library's code objects stay what they were. The call's schedule and scratch layout (the
+// temporal call's) are denoise_plan.h's.
 #pragma once
 
 namespace tr_tdemod {
-// bytes of scratch of a call for a width x height film: the temporal call's (tr_temporal::scratch_bytes), laid out as its own
-uint64_t scratch_bytes(uint32_t width, uint32_t height);
-// the three regions of that buffer
-struct Layout { void* centre; void* neighbour; void* sums; };
-Layout layout(void* scratch, uint32_t width, uint32_t height);
 // the two preparing launches of one frame: k_tdm_prepare (the records of the films divided by the scale of `albedo`), then k_dn_prepare<1>
 void prepare(hipStream_t stream, const float* even, const float* odd, const float* albedo, uint32_t width, uint32_t height, void* records);
 // one k_tdm_pass<patch> over all 32 x 16 tiles, as tr_temporal::pass; last: the normalised image times the scale of `albedo` (the centre frame's)

@@ -8,14 +8,6 @@
 
 namespace tr_tdemod {
 
-uint64_t scratch_bytes(uint32_t width, uint32_t height) { return tdm_scratch_bytes(width, height); }
-
-Layout layout(void* scratch, uint32_t width, uint32_t height) {
-    const size_t records = (size_t)dn_scratch_bytes(width, height);
-    char* const base = static_cast<char*>(scratch);
-    return {base, base + records, base + 2u * records};
-}
-
 void prepare(hipStream_t stream, const float* even, const float* odd, const float* albedo, uint32_t width, uint32_t height, void* records) {
     const float4* const e4 = reinterpret_cast<const float4*>(even);
     const float4* const o4 = reinterpret_cast<const float4*>(odd);

@@ -8,14 +8,6 @@
 
 namespace tr_temporal {
 
-uint64_t scratch_bytes(uint32_t width, uint32_t height) { return tdn_scratch_bytes(width, height); }
-
-Layout layout(void* scratch, uint32_t width, uint32_t height) {
-    const size_t records = (size_t)dn_scratch_bytes(width, height);
-    char* const base = static_cast<char*>(scratch);
-    return {base, base + records, base + 2u * records};
-}
-
 void pass(hipStream_t stream, const void* centre_records, const void* frame_records, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k,
           void* sums, bool first, bool last, float* out) {
     const float4* const c4 = static_cast<const float4*>(centre_records);

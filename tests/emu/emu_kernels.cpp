@@ -81,7 +81,9 @@ NOINSTR int emu_profile_dump(const char* path) {
 #include "../../tray_rust_amd/csrc/hip/kernels.hip"
 #include "../../tray_rust_amd/csrc/hip/kernel_select.h"   // the library's choice of the instantiation ...
 #include "../../tray_rust_amd/csrc/hip/launch_rules.h"    // ... its launch rules ...
-#include "../../tray_rust_amd/csrc/hip/scene_plan.h"      // ... and its per-scene decisions: the emulation applies them, it has no copy
+#include "../../tray_rust_amd/csrc/hip/scene_plan.h"      // ... its per-scene decisions ...
+#include "../../tray_rust_amd/csrc/hip/wavefront_plan.h"  // ... and its wavefront schedule: the emulation applies them, it has no copy
+#include "wavefront_plan_record.h"                        // (tests/test_wavefront_plan.py's exports)
 #ifdef TR_SAMPLE_RANGES   // (emu_sample_ranges.cpp) the kernels take a sample range: EMU_RANGE appends it to a call, and only there do the two builds differ
 #define EMU_RANGE(...) , __VA_ARGS__
 #else
@@ -160,6 +162,58 @@ void lds_layout(const TrayFlatScene* f, EmuScene& e, bool coop, bool film_rows) 
 
 using hip_emu::launch;
 using hip_emu::launch_simt;
+using tr_wfplan::QA; using tr_wfplan::QB; using tr_wfplan::QC; using tr_wfplan::QR; using tr_wfplan::Queue;
+
+// The wavefront schedule's Ops (wavefront_plan.h: round) of the emulation: the plan's launch groups as SIMT emulations over ONE view of the pool. After a
+// failed launch_simt nothing more is launched (rc). The traversal grid is the caller's, the fallback kernel runs as one workgroup.
+struct EmuWfOps {
+    const DevScene& d;
+    WfPool pool;
+    tr_wfplan::Buffers b;
+    WfChunk* chunks;
+    float* bins;
+    const uint2* tiles;
+    uint32_t n_items, tile_count, spp, kf;
+    float* rgbw;
+    uint32_t* counters;
+    DevStats* stats;
+    uint32_t slice_shift, smp_begin, smp_end;
+    uint32_t n_chunks, trace_blocks, lds_depth;
+    size_t fb_lds, bin_ctl_words;
+    WfBinGrid bin_grid;
+    int rc = 0;
+
+    template <class F> void k(uint32_t blocks, F&& f, size_t lds = 0) { if (rc == 0) rc = launch_simt(blocks, TR_BLOCK, f, lds); }
+    uint32_t q_blocks() const { return (n_chunks + WF_SEGS - 1u) / WF_SEGS * WF_SEGS; }   // grid of the one-thread-per-entry kernels
+    uint32_t bin_blocks() const { return (pool.seg_cap + WF_BIN_EPB - 1u) / WF_BIN_EPB * WF_SEGS; }
+    uint32_t n_active() const { return n_chunks * TR_BLOCK; }
+    uint32_t* qc(bool stage_c) const { return stage_c ? b.q[QC] : nullptr; }
+
+    template <int A> void advance() {
+        k(n_chunks, [&] { k_wf_advance<A>(d, pool, chunks, bins, tiles, n_items, tile_count, 1u, spp, kf, rgbw, counters, counters + 1, stats,
+                                          b.q[QA], b.q[QR], b.qctl, slice_shift EMU_RANGE(smp_begin, smp_end)); });
+    }
+    template <int A> void regen() {
+        k(q_blocks(), [&] { k_wf_regen<A>(d, pool, chunks, tiles, tile_count, 1u, spp, kf, stats, b.q[QR], b.q[QA], b.qctl, slice_shift); });
+    }
+    template <int S> void bin(Queue from, Queue to) {
+        uint32_t* const ctl = b.bin_ctl + (size_t)S * 2u * WF_SEGS * WF_BINS;
+        k(bin_blocks(), [&] { k_wf_bin_hist<S>(pool, b.q[from], b.qctl, ctl, bin_grid); });
+        k(bin_blocks(), [&] { k_wf_bin_scatter<S>(pool, b.q[from], b.q[to], b.qctl, ctl, bin_grid); });
+    }
+    template <int S, int A> void trace(Queue from, Queue fallback, uint32_t fused) {
+        k(trace_blocks, [&] { k_wf_trace_dyn<S, A>(d, pool, b.q[from], b.qctl, stats, lds_depth, b.overflow, b.q[fallback], fused); }, (size_t)lds_depth * TR_BLOCK * 4);
+        k(1u, [&] { k_wf_trace_fallback<S, A>(d, pool, b.qctl, b.q[fallback], fused); }, fb_lds);
+        g_wf_deferred += b.qctl[WF_FB_WORD + S];
+    }
+    int clear_qctl() { std::memset(b.qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t)); return 0; }
+    int clear_bin_ctl() { std::memset(b.bin_ctl, 0, bin_ctl_words * sizeof(uint32_t)); return 0; }
+    void sort() { k(n_chunks, [&] { k_wf_sort<0>(d, pool, n_active(), b.qctl, b.kq); }); }
+    template <int A, int K> void shade_kind() { k(q_blocks(), [&] { k_wf_shade_kind<A, K>(d, pool, b.kq, b.qctl, stats, b.q[QA], b.q[QB]); }); }
+    template <int A> void begin() { k(n_chunks, [&] { k_wf_begin<A>(d, pool, n_active(), stats, b.q[QB], b.qctl, b.kq); }); }
+    template <int A, int K> void query_kind(bool stage_c) { k(q_blocks(), [&] { k_wf_query_kind<A, K>(d, pool, b.kq, qc(stage_c), b.qctl, stats, b.q[QA]); }); }
+    template <int A> void query(bool stage_c) { k(n_chunks, [&] { k_wf_query<A, FEAT_ALL | FEAT_TEX>(d, pool, n_active(), qc(stage_c), b.qctl, stats, b.q[QA]); }); }
+};
 
 }  // namespace
 
@@ -319,7 +373,7 @@ int emu_wf_trace(const TrayFlatScene* f, int stage, uint32_t n, const TrayRay* r
     std::vector<uint32_t> fallback((size_t)n_slots * WF_RAY_WORDS, 0u);   // records of the deferred rays (on the device: the buffer of a ray queue that is idle during the stage)
     std::vector<DevStats> stats(WF_STAT_SLOTS);
     std::memset(stats.data(), 0, stats.size() * sizeof(DevStats));
-    // (the traversal, then the rays it handed to the reference's binary traversal: wf_round of device_api.hip)
+    // (the traversal, then the rays it handed to the reference's binary traversal: round of wavefront_plan.h)
 #define EMU_TRACE(S) do { launch(blocks, TR_BLOCK, [&] { k_wf_trace_dyn<S, 0>(e.d, pool, queue.data(), qctl.data(), stats.data(), lds_depth, overflow.data(), fallback.data(), 0u); }); \
                           launch(2, TR_BLOCK, [&] { k_wf_trace_fallback<S, 0>(e.d, pool, qctl.data(), fallback.data(), 0u); }); } while (0)
     if (stage == 0) EMU_TRACE(0); else if (stage == 1) EMU_TRACE(1); else EMU_TRACE(2);
@@ -427,9 +481,10 @@ int emu_render_tiles(const TrayFlatScene* f, const uint32_t* tiles_xy, uint32_t 
     return render_tiles(f, tiles_xy, tile_count, spp, 0u, 0u, seed, rgbw, blocks, coop, film_rows, stats_out, shard, n_shards, chunk_tiles);
 }
 
-// The wavefront schedule (launch_wavefront + wf_round of device_api.hip): rounds of k_wf_advance -> k_wf_regen -> trace A ->
-// k_wf_begin -> trace B -> k_wf_query -> trace C over an HBM-style path pool until every tile is done. All kernels run as SIMT
-// emulations (`trace` is kept in the signature: 0 = k_wf_trace_dyn, the only traversal kernel). Moving scenes run the ANIM = 1 kernels with
+// The wavefront schedule as launch_wavefront of device_api.hip runs it -- the rules, the buffers' layout, a round's launches and the loop are the one
+// copy in wavefront_plan.h -- as view 0 of 1 over an HBM-style path pool until every tile is done. What differs from the library is the emulation's own:
+// the kernels run as SIMT emulations (EmuWfOps; `trace` is kept in the signature: 0 = k_wf_trace_dyn, the only traversal kernel), the buffers are
+// vectors of the plan's sizes, and completion is looked at after every round, not every WF_POLL rounds. Moving scenes run the ANIM = 1 kernels with
 // the per-slot transform cache.
 // n_chunks = 256-slot chunks of the pool (<= tile_count); lds_depth as in emu_wf_trace. [smp_begin, smp_end): the samples of the spp-sample frame to
 // render, 0 / 0 = all of them.
@@ -445,7 +500,7 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
     const uint32_t slice_shift = tr_rules::wf_slice_shift(tile_count, n_chunks, n_smp, 0u);
     const uint32_t n_items = tile_count << slice_shift;
     n_chunks = std::max(1u, std::min(n_chunks, n_items));
-    const uint32_t n_slots = n_chunks * TR_BLOCK, n_active = n_slots;
+    const uint32_t n_slots = n_chunks * TR_BLOCK;
     std::vector<float> pool_data((size_t)F_COUNT * n_slots, 0.0f);
     WfPool pool{pool_data.data(), n_slots, wf_seg_cap(n_chunks)};
     const std::vector<uint32_t>& moving_ids = e.plan.moving_ids;
@@ -464,10 +519,6 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
     }
     std::vector<WfChunk> chunks(n_chunks, WfChunk{WF_TILE_NEED, 0u});
     std::vector<float> bins((size_t)n_chunks * ROWBIN_SIZE, 0.0f);
-    const size_t q_cap = (size_t)WF_SEGS * pool.seg_cap;
-    const uint32_t q_blocks = (n_chunks + WF_SEGS - 1u) / WF_SEGS * WF_SEGS;   // grid of the one-thread-per-entry kernels (launch_wavefront)
-    std::vector<uint32_t> queues((3 * WF_RAY_WORDS + 1) * q_cap + WF_QCTL_WORDS, 0u);   // ray queues A, B, C (the rays themselves), regeneration queue (slot indices)
-    uint32_t* const qa = queues.data(), * const qb = qa + WF_RAY_WORDS * q_cap, * const qc = qb + WF_RAY_WORDS * q_cap, * const qr = qc + WF_RAY_WORDS * q_cap, * const qctl = qr + q_cap;
     uint32_t counters[2] = {0u, 0u};
     std::vector<DevStats> stats(WF_STAT_SLOTS);
     std::memset(stats.data(), 0, stats.size() * sizeof(DevStats));
@@ -477,77 +528,25 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
     const uint32_t full = e.quad_words;
     if (lds_depth == 0 || lds_depth > full) lds_depth = full;
     trace_blocks = std::max(1u, std::min(trace_blocks, n_chunks));
-    std::vector<uint32_t> overflow((size_t)(full + 64u) * trace_blocks * TR_BLOCK, 0u);
-    const size_t fb_lds = (size_t)e.plan.depth * TR_BLOCK * 4;
-    const size_t dyn_lds = (size_t)lds_depth * TR_BLOCK * 4;
-    const int feat = e.plan.feat;
-    // the material sort of the shading stage (default of the library for the compacted schedule; trace == 2 is the slot form without queues)
     if (trace != 0) return -6;
-    const bool sorted = !(feat & FEAT_TEX);
-    std::vector<uint32_t> kind_queues((size_t)WF_MAT_KINDS * q_cap, 0u);
-    const uint32_t kinds_present = e.plan.mat_kinds_present;
-    const uint64_t max_rounds = (uint64_t)((n_items + n_chunks - 1) / n_chunks) * (((uint64_t)n_smp + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * e.d.max_depth + 3) + 4) + 32;
+    // the buffers, of the plan's sizes and cut as its view 0 of 1
+    const tr_wfplan::Layout lay = tr_wfplan::layout(n_chunks, std::max(full, 8u), lds_depth, trace_blocks);
+    const tr_wfplan::View view = tr_wfplan::view(lay, 0u, 1u, n_chunks);
+    const bool sorted = !(e.plan.feat & FEAT_TEX);   // the material sort of the shading stage
+    std::vector<uint32_t> queues(lay.queue_bytes / 4u, 0u), kind_queues(sorted ? lay.kind_bytes / 4u : 0u, 0u), bin_ctl(lay.bin_ctl_bytes / 4u, 0u), overflow(lay.ovf_bytes / 4u, 0u);
+    const WfBinGrid bin_grid = f->n_top_nodes ? wf_bin_grid(f->top_nodes[0].bmin, f->top_nodes[0].bmax) : WfBinGrid{};
+    EmuWfOps ops{e.d, pool, tr_wfplan::buffers(lay, view, queues.data(), sorted ? kind_queues.data() : nullptr, bin_ctl.data(), overflow.data()), chunks.data(), bins.data(),
+                 tiles.data(), n_items, tile_count, spp, kf, rgbw, counters, stats.data(), slice_shift, smp_begin, smp_end, n_chunks, trace_blocks, lds_depth,
+                 (size_t)e.plan.depth * TR_BLOCK * 4, (size_t)lay.bin_ctl_words, bin_grid};
+    const tr_wfplan::RoundCfg cfg{sorted, tr_wfplan::fused_wanted(), tr_wfplan::bin_stages_wanted(), true, e.plan.mat_kinds_present};
+    const uint64_t max_rounds = tr_wfplan::max_rounds(n_items, n_chunks, n_smp, slice_shift, e.d.max_depth);
+    const auto poll = [&]() -> int { return ops.rc != 0 ? -1 : counters[1] >= n_items ? 1 : 0; };
     int rc = 0;
     uint64_t rounds = 0;
-    // ray binning before the traversal stages, as launch_wavefront sets it up (TRAYHIP_WF_BIN: bit 0 = stage A, bit 1 = stage B)
-    bool fused = sorted && WF_FOLD_C && WF_FUSED_DEFAULT != 0;   // launch_wavefront's choice of the shading form (TRAYHIP_WF_FUSED)
-    if (const char* fe = getenv("TRAYHIP_WF_FUSED")) fused = sorted && WF_FOLD_C && atoi(fe) != 0;
-    uint32_t bin_stages = WF_BIN_DEFAULT;
-    if (const char* be = getenv("TRAYHIP_WF_BIN")) bin_stages = (uint32_t)std::max(0, atoi(be)) & 3u;
-    std::vector<uint32_t> bin_ctl((size_t)2u * 2u * WF_SEGS * WF_BINS, 0u);
-    const WfBinGrid bin_grid = f->n_top_nodes ? wf_bin_grid(f->top_nodes[0].bmin, f->top_nodes[0].bmax) : WfBinGrid{};
-    const uint32_t bin_blocks = (pool.seg_cap + WF_BIN_EPB - 1u) / WF_BIN_EPB * WF_SEGS;
-#define EMU_K(...) do { if (rc == 0) rc = launch_simt(__VA_ARGS__); } while (0)
-#define EMU_ROUND(A)                                                                                                                        \
-    do {                                                                                                                                    \
-        EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_advance<A>(e.d, pool, chunks.data(), bins.data(), tiles.data(), n_items, tile_count, 1u, spp, kf, rgbw, \
-                                                         counters, counters + 1, stats.data(), qa, qr, qctl, slice_shift EMU_RANGE(smp_begin, smp_end)); }); \
-        EMU_K(q_blocks, TR_BLOCK, [&] { k_wf_regen<A>(e.d, pool, chunks.data(), tiles.data(), tile_count, 1u, spp, kf, stats.data(), qr, qa, qctl, slice_shift); }); \
-        if (WF_FOLD_C && (bin_stages & 1u)) { EMU_BIN(0, qa, qc, bin_ctl.data()); EMU_TRACE_STAGE(0, A, qc, qb); }   /* wf_round: the binned copy lies in the idle queue's buffer */ \
-        else EMU_TRACE_STAGE(0, A, qa, qb);                                                                                                   \
-        std::memset(qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t));   /* wf_round: the control words are cleared between trace A and k_wf_begin */ \
-        if (fused) {   /* wf_round: k_wf_sort + k_wf_shade_kind, then the occlusion stage */                                                  \
-            EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_sort<0>(e.d, pool, n_active, qctl, kind_queues.data()); });                                 \
-            EMU_SHADE_KIND(A, TRAY_MAT_MATTE); EMU_SHADE_KIND(A, TRAY_MAT_PLASTIC); EMU_SHADE_KIND(A, TRAY_MAT_METAL); EMU_SHADE_KIND(A, TRAY_MAT_GLASS); \
-            EMU_SHADE_KIND(A, TRAY_MAT_ROUGH_GLASS); EMU_SHADE_KIND(A, TRAY_MAT_SPECULAR_METAL); EMU_SHADE_KIND(A, TRAY_MAT_MERL);          \
-            EMU_TRACE_STAGE(1, A, qb, qc);                                                                                                  \
-            break;                                                                                                                          \
-        }                                                                                                                                   \
-        EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_begin<A>(e.d, pool, n_active, stats.data(), qb, qctl, sorted ? kind_queues.data() : nullptr); }); \
-        if (WF_FOLD_C && (bin_stages & 2u)) { EMU_BIN(1, qb, qa, bin_ctl.data() + 2u * WF_SEGS * WF_BINS); EMU_TRACE_STAGE(1, A, qa, qc); }     \
-        else EMU_TRACE_STAGE(1, A, qb, qc);                                                                                                   \
-        if (sorted) {   /* wf_round: one kind-pure                shading launch per material kind of the scene */                        \
-            EMU_QUERY_KIND(A, TRAY_MAT_MATTE); EMU_QUERY_KIND(A, TRAY_MAT_PLASTIC); EMU_QUERY_KIND(A, TRAY_MAT_METAL); EMU_QUERY_KIND(A, TRAY_MAT_GLASS); \
-            EMU_QUERY_KIND(A, TRAY_MAT_ROUGH_GLASS); EMU_QUERY_KIND(A, TRAY_MAT_SPECULAR_METAL); EMU_QUERY_KIND(A, TRAY_MAT_MERL);          \
-        } else EMU_K(n_chunks, TR_BLOCK, [&] { k_wf_query<A, FEAT_ALL | FEAT_TEX>(e.d, pool, n_active, WF_FOLD_C ? nullptr : qc, qctl, stats.data(), qa); });  \
-        if (!WF_FOLD_C) EMU_TRACE_STAGE(2, A, qc, qb);                                                                                                        \
-    } while (0)
-#define EMU_SHADE_KIND(A, K) do { if (kinds_present & (1u << K)) EMU_K(q_blocks, TR_BLOCK, [&] { k_wf_shade_kind<A, K>(e.d, pool, kind_queues.data(), qctl, stats.data(), qa, qb); }); } while (0)
-#define EMU_QUERY_KIND(A, K) do { if (kinds_present & (1u << K)) EMU_K(q_blocks, TR_BLOCK, [&] { k_wf_query_kind<A, K>(e.d, pool, kind_queues.data(), WF_FOLD_C ? nullptr : qc, qctl, stats.data(), qa); }); } while (0)
-#define EMU_TRACE_STAGE(S, A, Q, FB) /* FB: the queue buffer that is idle during stage S takes the deferred rays' records (wf_round) */                                                                                                          \
-    do {                                                                                                                                    \
-        const uint32_t fu_ = (S == 1 && fused) ? 1u : 0u;                                                                                   \
-        EMU_K(trace_blocks, TR_BLOCK, [&] { k_wf_trace_dyn<S, A>(e.d, pool, Q, qctl, stats.data(), lds_depth, overflow.data(), FB, fu_); }, dyn_lds); \
-        EMU_K(1u, TR_BLOCK, [&] { k_wf_trace_fallback<S, A>(e.d, pool, qctl, FB, fu_); }, fb_lds);                                    \
-        g_wf_deferred += qctl[WF_FB_WORD + S];                                                                                              \
-    } while (0)
-#define EMU_BIN(S, Q, OUT, CTL) /* ray binning before stage S (wavefront.h: k_wf_bin_hist / k_wf_bin_scatter) */                          \
-    do {                                                                                                                                    \
-        EMU_K(bin_blocks, TR_BLOCK, [&] { k_wf_bin_hist<S>(pool, Q, qctl, CTL, bin_grid); });                                               \
-        EMU_K(bin_blocks, TR_BLOCK, [&] { k_wf_bin_scatter<S>(pool, Q, OUT, qctl, CTL, bin_grid); });                                       \
-    } while (0)
-    std::memset(qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t));
-    while (rc == 0 && counters[1] < n_items) {
-        std::fill(bin_ctl.begin(), bin_ctl.end(), 0u);
-        if (moving) EMU_ROUND(1); else EMU_ROUND(0);
-        if (++rounds > max_rounds) rc = -5;   // "wavefront schedule did not terminate"
+    if (counters[1] < n_items) {   // (a launch without work items runs no round)
+        const tr_wfplan::Ended ended = moving ? tr_wfplan::run<1>(&ops, 1u, cfg, max_rounds, 1u, poll, &rounds) : tr_wfplan::run<0>(&ops, 1u, cfg, max_rounds, 1u, poll, &rounds);
+        rc = ops.rc != 0 ? ops.rc : ended == tr_wfplan::kNotTerminated ? -5 : 0;   // -5: "wavefront schedule did not terminate"
     }
-#undef EMU_BIN
-#undef EMU_TRACE_STAGE
-#undef EMU_QUERY_KIND
-#undef EMU_SHADE_KIND
-#undef EMU_ROUND
-#undef EMU_K
     if (stats_out) {
         DevStats st{};
         for (const DevStats& a : stats) { st.samples += a.samples; st.vertices += a.vertices; st.rays += a.rays; }

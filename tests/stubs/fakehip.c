@@ -11,6 +11,8 @@
  * add-on libraries (tests/test_guide_stub.py, test_denoise_stub.py, test_noise_target_stub.py), "launch ... lds=<dynamic LDS bytes> kernel=<symbol>" for
  * everything else (tests/test_scene_plan_stub.py); under
  * FAKEHIP_TILE_KERNEL=1 a "range dev=.. begin=.. end=.." line goes in front of the tile kernel's "launch" line (tests/test_sample_ranges_stub.py).
+ * FAKEHIP_LOG_MEM=1 adds a "malloc bytes=.. ptr=.." line per hipMalloc and a "memset ptr=.. value=.. bytes=.. stream=.." line per hipMemsetAsync
+ * (tools/wf_stub_logs.py: a launch's whole host-side footprint, to compare two builds of the library).
  * A new add-on library gets a branch of its own in hipLaunchKernel. tests/_stub.py builds and preloads this file. */
 #define _GNU_SOURCE
 #include <dlfcn.h>
@@ -46,6 +48,7 @@ hipError_t hipMalloc(void** p, size_t n) {
     const char* e = getenv("FAKEHIP_MALLOC_MAX");
     if (e && n > strtoull(e, NULL, 10)) { *p = NULL; logf_("malloc_refused bytes=%zu", n); return 2; }
     *p = calloc(n ? n : 1, 1);
+    if (getenv("FAKEHIP_LOG_MEM")) logf_("malloc bytes=%zu ptr=%p", n, *p);
     return *p ? 0 : 2;
 }
 hipError_t hipFree(void* p) { free(p); return 0; }
@@ -59,7 +62,11 @@ hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int kind, hipStream_
     return 0;
 }
 hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) { (void)st; memset(d, v, n); return 0; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st) {
+    if (getenv("FAKEHIP_LOG_MEM")) logf_("memset ptr=%p value=%d bytes=%zu stream=%p", d, v, n, st);
+    memset(d, v, n);
+    return 0;
+}
 hipError_t hipMemGetInfo(size_t* fr, size_t* tot) {
     const char* e = getenv("FAKEHIP_FREE_BYTES");
     *fr = e ? (size_t)strtoull(e, NULL, 10) : (size_t)1 << 36;

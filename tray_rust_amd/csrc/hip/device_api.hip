@@ -23,11 +23,9 @@
 #include "launch_rules.h"
 #include "scene_plan.h"
 #include "denoise_plan.h"
+#include "wavefront_plan.h"   // (WF_PIPES_MAX, WF_POLL)
 
 
-#ifndef WF_PIPES_MAX
-#define WF_PIPES_MAX 4   // views of the wavefront schedule (WfView below) the buffers are sized for
-#endif
 struct TrayDevBuf { const char* key; void* ptr; size_t bytes; };
 // What tray_scene_update_frame requires of its argument: the SAME scene at another frame. The device buffers a frame update takes
 // over without a copy (meshes, trees, triangles, MERL tables, textures, permutation pool, filter tables) are recognised by name and size
@@ -67,7 +65,8 @@ struct WfBuffers {   // the wavefront schedule's pool and the buffers that go wi
     uint32_t* d_queues = nullptr;        // ray queues A, B, C (n_slots each) + WF_QCTL_WORDS counters
     uint32_t* d_kind_queues = nullptr;   // WF_MAT_KINDS x n_slots slot indices
     uint32_t* d_bin_ctl = nullptr;       // ray binning before the traversal stages (wavefront.h: k_wf_bin_hist): per view and stage, histogram + cursors of every segment
-    uint32_t* d_stack_overflow = nullptr; size_t ovf_entries = 0;   // entries per view of the schedule (WF_PIPES_MAX of them)
+    uint32_t* d_stack_overflow = nullptr;
+    tr_wfplan::Layout lay{};             // where the views' parts of d_queues, d_kind_queues, d_bin_ctl and d_stack_overflow lie (wavefront_plan.h)
     uint32_t n_blocks_trace = 0;         // persistent grid of k_wf_trace_dyn
     uint32_t trace_lds_depth = 0, trace_lds_bytes = 0;   // LDS part of the dynamic-fetch kernel's stacks; deeper entries go to d_stack_overflow
     bool wf_sort = true;                 // material sort of the shading stage (k_wf_begin's LDS counting sort -> k_wf_query_kind); off for textured scenes
@@ -209,92 +208,69 @@ static int upload(TrayDeviceScene* s, const char* key, bool unchanged, const T* 
 // idle): launch_wavefront cuts tiles until the items fill the chunks and no further (profiles/r06_c5_pool_64m.txt, r06_c5_pool_128m.txt).
 #define WF_SLOTS (128u << 20)
 #endif
-#define WF_POLL 16
-// one round of the wavefront schedule: advance -> regen -> trace A -> begin -> trace B -> query -> trace C (compacted ray queues, persistent
-// traversal with dynamic fetch, kind-pure shading over the material sort's queues; scenes with textured materials, whose lobes
-// exist per hit only, shade unsorted in the one instantiation that lowers them)
-// A VIEW of the wavefront buffers: a range of the pool's chunks with queues, control words and overflow columns of its own. The schedule
-// runs WF_PIPES views, each on its own stream: every stage kernel ends with the tail of its slowest rays (trace C is nearly all
-// tail: a few thousand rays, ~600 us for the longest chain of dependent fetches), and while one view's kernel drains, the
-// workgroups it frees run the other view's kernels. The views share the tile counter, so the split does not unbalance them.
-struct WfView {
+using tr_wfplan::QA; using tr_wfplan::QB; using tr_wfplan::QC; using tr_wfplan::QR; using tr_wfplan::Queue;
+// What every view of a wavefront launch renders: the arguments of launch_wavefront
+struct WfLaunch {
+    const uint2* tiles;
+    uint32_t tile_count, chunk, chunk_stride, spp, kf;   // tile_count: work items
+    float* rgbw_dev;
+    uint32_t slice_shift, smp_begin, smp_end;
+};
+// A view of the wavefront buffers (wavefront_plan.h: View) as the Ops of tr_wfplan::round: the plan's launch groups on the view's stream
+struct WfOps {
+    TrayDeviceScene* s;
+    const WfLaunch* a;
     DevScene dev;       // the scene with xf_cache moved to the view's first slot
     WfPool pool;        // data moved to the view's first slot, n_slots = the pool's stride, seg_cap of the view's chunks
     WfChunk* chunks;
     float* bins;
-    uint32_t *qa, *qb, *qc, *qr, *qctl, *kq, *overflow, *fallback, *bin_ctl;
+    tr_wfplan::Buffers b;
     uint32_t n_chunks;
     hipStream_t stream;
+
+    const WfBuffers& w() const { return s->lb.wf; }
+    dim3 block() const { return dim3(TR_BLOCK); }
+    dim3 grid() const { return dim3(n_chunks); }
+    dim3 qgrid() const { return dim3((n_chunks + WF_SEGS - 1u) / WF_SEGS * WF_SEGS); }   // one-thread-per-entry kernels: block b reads segment b % WF_SEGS
+    dim3 tgrid() const { return dim3(std::min<uint32_t>(w().n_blocks_trace, n_chunks)); }
+    dim3 bgrid() const { return dim3((pool.seg_cap + WF_BIN_EPB - 1u) / WF_BIN_EPB * WF_SEGS); }
+    uint32_t n_active() const { return n_chunks * TR_BLOCK; }
+    uint32_t* qc(bool stage_c) const { return stage_c ? b.q[QC] : nullptr; }
+
+    template <int ANIM> void advance() {
+        uint32_t* const counters = w().d_wf_counters;
+        if (a->smp_end) tr_ranges::wf_advance(ANIM, grid(), block(), stream, dev, pool, chunks, bins, a->tiles, a->tile_count, a->chunk, a->chunk_stride,   // (a sample range)
+                                              a->spp, a->kf, a->rgbw_dev, counters, counters + 1, s->d_stats, b.q[QA], b.q[QR], b.qctl, a->slice_shift, a->smp_begin, a->smp_end);
+        else hipLaunchKernelGGL(k_wf_advance<ANIM>, grid(), block(), 0, stream, dev, pool, chunks, bins, a->tiles, a->tile_count, a->chunk, a->chunk_stride,
+                                a->spp, a->kf, a->rgbw_dev, counters, counters + 1, s->d_stats, b.q[QA], b.q[QR], b.qctl, a->slice_shift);
+    }
+    template <int ANIM> void regen() {
+        hipLaunchKernelGGL(k_wf_regen<ANIM>, qgrid(), block(), 0, stream, dev, pool, chunks, a->tiles, a->chunk, a->chunk_stride, a->spp, a->kf, s->d_stats,
+                           b.q[QR], b.q[QA], b.qctl, a->slice_shift);
+    }
+    template <int S> void bin(Queue from, Queue to) {
+        uint32_t* const ctl = b.bin_ctl + (size_t)S * 2u * WF_SEGS * WF_BINS;
+        hipLaunchKernelGGL(k_wf_bin_hist<S>, bgrid(), block(), 0, stream, pool, b.q[from], b.qctl, ctl, s->bin_grid);
+        hipLaunchKernelGGL(k_wf_bin_scatter<S>, bgrid(), block(), 0, stream, pool, b.q[from], b.q[to], b.qctl, ctl, s->bin_grid);
+    }
+    template <int S, int ANIM> void trace(Queue from, Queue fallback, uint32_t fused) {
+        hipLaunchKernelGGL((k_wf_trace_dyn<S, ANIM>), tgrid(), block(), w().trace_lds_bytes, stream, dev, pool, b.q[from], b.qctl, s->d_stats, w().trace_lds_depth, b.overflow, b.q[fallback], fused);
+        hipLaunchKernelGGL((k_wf_trace_fallback<S, ANIM>), dim3(8), block(), s->stack_bytes, stream, dev, pool, b.qctl, b.q[fallback], fused);
+    }
+    int clear_qctl() { HIP_CHECK(hipMemsetAsync(b.qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t), stream)); return TRAY_OK; }
+    int clear_bin_ctl() { HIP_CHECK(hipMemsetAsync(b.bin_ctl, 0, (size_t)w().lay.bin_ctl_words * sizeof(uint32_t), stream)); return TRAY_OK; }
+    void sort() { hipLaunchKernelGGL(k_wf_sort<0>, grid(), block(), 0, stream, dev, pool, n_active(), b.qctl, b.kq); }
+    template <int ANIM, int K> void shade_kind() {
+        hipLaunchKernelGGL((k_wf_shade_kind<ANIM, K>), qgrid(), block(), 0, stream, dev, pool, b.kq, b.qctl, s->d_stats, b.q[QA], b.q[QB]);
+    }
+    template <int ANIM> void begin() { hipLaunchKernelGGL(k_wf_begin<ANIM>, grid(), block(), 0, stream, dev, pool, n_active(), s->d_stats, b.q[QB], b.qctl, b.kq); }
+    template <int ANIM, int K> void query_kind(bool stage_c) {
+        hipLaunchKernelGGL((k_wf_query_kind<ANIM, K>), qgrid(), block(), 0, stream, dev, pool, b.kq, qc(stage_c), b.qctl, s->d_stats, b.q[QA]);
+    }
+    template <int ANIM> void query(bool stage_c) {
+        hipLaunchKernelGGL((k_wf_query<ANIM, FEAT_ALL | FEAT_TEX>), grid(), block(), 0, stream, dev, pool, n_active(), qc(stage_c), b.qctl, s->d_stats, b.q[QA]);
+    }
 };
-template <int ANIM>
-static void wf_round(TrayDeviceScene* s, const WfView& v, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride, uint32_t spp,
-                     uint32_t kf, float* rgbw_dev, uint32_t slice_shift, uint32_t smp_begin, uint32_t smp_end) {
-    const WfBuffers& w = s->lb.wf;
-    const dim3 grid(v.n_chunks), block(TR_BLOCK);
-    const dim3 qgrid((v.n_chunks + WF_SEGS - 1u) / WF_SEGS * WF_SEGS);   // one-thread-per-entry kernels: block b reads segment b % WF_SEGS
-    const dim3 tgrid(std::min<uint32_t>(w.n_blocks_trace, v.n_chunks));
-    const uint32_t n_active = v.n_chunks * TR_BLOCK;
-    hipStream_t stream = v.stream;
-    if (smp_end) tr_ranges::wf_advance(ANIM, grid, block, stream, v.dev, v.pool, v.chunks, v.bins, tiles, tile_count, chunk, chunk_stride,   // (a sample range)
-                                       spp, kf, rgbw_dev, w.d_wf_counters, w.d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift, smp_begin, smp_end);
-    else hipLaunchKernelGGL(k_wf_advance<ANIM>, grid, block, 0, stream, v.dev, v.pool, v.chunks, v.bins, tiles, tile_count, chunk, chunk_stride,
-                            spp, kf, rgbw_dev, w.d_wf_counters, w.d_wf_counters + 1, s->d_stats, v.qa, v.qr, v.qctl, slice_shift);
-    hipLaunchKernelGGL(k_wf_regen<ANIM>, qgrid, block, 0, stream, v.dev, v.pool, v.chunks, tiles, chunk, chunk_stride, spp, kf, s->d_stats, v.qr, v.qa, v.qctl, slice_shift);
-    // (each traversal is followed by the few-thread kernel that traces the rays it handed over to the reference's binary traversal:
-    // direction components that are zero / denormal / not finite -- normally none, the kernel reads one word and exits. The deferred rays'
-    // records go to the buffer of a ray queue that is idle during the stage: B's during A, C's during B, B's during C)
-    const dim3 fgrid(8);
-    // ray binning (wavefront.h: k_wf_bin_hist / k_wf_bin_scatter): the stage's queue, every segment sorted by (origin cell, direction octant) into the
-    // ray queue that is idle during the stage -- C's for stage A (WF_FOLD_C: nobody fills it), A's for stage B (consumed by then) --, which is what
-    // the traversal then draws from; the fallback records go where they went (B's buffer during A, C's during B: the sorted copy is consumed by then)
-    const dim3 bgrid((v.pool.seg_cap + WF_BIN_EPB - 1u) / WF_BIN_EPB * WF_SEGS);
-    const uint32_t* trace_a = v.qa;
-    if (WF_FOLD_C && v.bin_ctl && (s->wf_bin_stages & 1u)) {
-        hipLaunchKernelGGL(k_wf_bin_hist<0>, bgrid, block, 0, stream, v.pool, v.qa, v.qctl, v.bin_ctl, s->bin_grid);
-        hipLaunchKernelGGL(k_wf_bin_scatter<0>, bgrid, block, 0, stream, v.pool, v.qa, v.qc, v.qctl, v.bin_ctl, s->bin_grid);
-        trace_a = v.qc;
-    }
-    hipLaunchKernelGGL((k_wf_trace_dyn<0, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, trace_a, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qb, 0u);
-    hipLaunchKernelGGL((k_wf_trace_fallback<0, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qb, 0u);
-    // the control words of every queue are cleared HERE, between the traversal of stage A and the first shading kernel: queue A, its cursors, the
-    // regeneration queue and stage A's fallback counter are consumed, stage B's and the material kinds' are not produced yet -- and the count of
-    // queue A must survive from the query kernels below (which append the NEXT round's continuation rays) to the next round's traversal
-    (void)hipMemsetAsync(v.qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t), stream);
-    // Fused shading (wavefront.h: k_wf_sort + k_wf_shade_kind; scenes whose materials are sorted by kind, i.e. without textured ones): the vertex is shaded in ONE
-    // kernel between the two traversals, its light term pending until the occlusion ray is traced; TRAYHIP_WF_FUSED=0: the two-kernel form of rounds 2-5
-    const uint32_t fused = (v.kq && s->wf_fused && WF_FOLD_C) ? 1u : 0u;
-    if (fused) {
-        hipLaunchKernelGGL(k_wf_sort<0>, grid, block, 0, stream, v.dev, v.pool, n_active, v.qctl, v.kq);
-#define WF_SHADE_KIND(K) if (s->mat_kinds_present & (1u << K)) hipLaunchKernelGGL((k_wf_shade_kind<ANIM, K>), qgrid, block, 0, stream, v.dev, v.pool, v.kq, v.qctl, s->d_stats, v.qa, v.qb)
-        WF_SHADE_KIND(TRAY_MAT_MATTE); WF_SHADE_KIND(TRAY_MAT_PLASTIC); WF_SHADE_KIND(TRAY_MAT_METAL); WF_SHADE_KIND(TRAY_MAT_GLASS);
-        WF_SHADE_KIND(TRAY_MAT_ROUGH_GLASS); WF_SHADE_KIND(TRAY_MAT_SPECULAR_METAL); WF_SHADE_KIND(TRAY_MAT_MERL);
-#undef WF_SHADE_KIND
-        hipLaunchKernelGGL((k_wf_trace_dyn<1, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, v.qb, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qc, 1u);
-        hipLaunchKernelGGL((k_wf_trace_fallback<1, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qc, 1u);
-        return;
-    }
-    hipLaunchKernelGGL(k_wf_begin<ANIM>, grid, block, 0, stream, v.dev, v.pool, n_active, s->d_stats, v.qb, v.qctl, v.kq);
-    const uint32_t* trace_b = v.qb;
-    if (WF_FOLD_C && v.bin_ctl && (s->wf_bin_stages & 2u)) {
-        uint32_t* const ctl_b = v.bin_ctl + 2u * WF_SEGS * WF_BINS;
-        hipLaunchKernelGGL(k_wf_bin_hist<1>, bgrid, block, 0, stream, v.pool, v.qb, v.qctl, ctl_b, s->bin_grid);
-        hipLaunchKernelGGL(k_wf_bin_scatter<1>, bgrid, block, 0, stream, v.pool, v.qb, v.qa, v.qctl, ctl_b, s->bin_grid);
-        trace_b = v.qa;
-    }
-    hipLaunchKernelGGL((k_wf_trace_dyn<1, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, trace_b, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qc, 0u);
-    hipLaunchKernelGGL((k_wf_trace_fallback<1, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qc, 0u);
-    uint32_t* const qc = WF_FOLD_C ? nullptr : v.qc;   // (WF_FOLD_C: stage C rays travel with the next round's stage A rays, no queue and no launch of their own)
-    if (v.kq) {   // kind-pure shading over the sorted queues: one launch per material kind the scene contains
-#define WF_QUERY_KIND(K) if (s->mat_kinds_present & (1u << K)) hipLaunchKernelGGL((k_wf_query_kind<ANIM, K>), qgrid, block, 0, stream, v.dev, v.pool, v.kq, qc, v.qctl, s->d_stats, v.qa)
-        WF_QUERY_KIND(TRAY_MAT_MATTE); WF_QUERY_KIND(TRAY_MAT_PLASTIC); WF_QUERY_KIND(TRAY_MAT_METAL); WF_QUERY_KIND(TRAY_MAT_GLASS);
-        WF_QUERY_KIND(TRAY_MAT_ROUGH_GLASS); WF_QUERY_KIND(TRAY_MAT_SPECULAR_METAL); WF_QUERY_KIND(TRAY_MAT_MERL);
-#undef WF_QUERY_KIND
-    } else hipLaunchKernelGGL((k_wf_query<ANIM, FEAT_ALL | FEAT_TEX>), grid, block, 0, stream, v.dev, v.pool, n_active, qc, v.qctl, s->d_stats, v.qa);
-    if (WF_FOLD_C) return;
-    // (builds without WF_FOLD_C: the deferred rays of stage C go to B's buffer -- A's holds the next round's continuation rays by now)
-    hipLaunchKernelGGL((k_wf_trace_dyn<2, ANIM>), tgrid, block, w.trace_lds_bytes, stream, v.dev, v.pool, v.qc, v.qctl, s->d_stats, w.trace_lds_depth, v.overflow, v.qb, 0u);
-    hipLaunchKernelGGL((k_wf_trace_fallback<2, ANIM>), fgrid, block, s->stack_bytes, stream, v.dev, v.pool, v.qctl, v.qb, 0u);
-}
 
 // Path pool slots of the wavefront schedule: never more than the film has pixels x 4 x WF_MAX_SLICES (a chunk of 256 per tile slice), and for
 // moving scenes never more than the per-path transform cache (112 B per slot and instance that moves within the frame) can hold within two
@@ -525,10 +501,8 @@ static int scene_plan(const TrayFlatScene* f, TrayDeviceScene* s, const std::vec
     s->stack_bytes = p.stack_bytes; s->dev.coop_offset = p.coop_offset; s->dev.win_offset = p.win_offset;
     // ray binning before the traversal stages (wavefront.h): the cells are those of the frame's BVH<Instance> root box
     s->bin_grid = f->n_top_nodes ? wf_bin_grid(f->top_nodes[0].bmin, f->top_nodes[0].bmax) : WfBinGrid{};
-    s->wf_bin_stages = WF_BIN_DEFAULT;
-    if (const char* e = getenv("TRAYHIP_WF_BIN")) s->wf_bin_stages = (uint32_t)std::max(0, atoi(e)) & 3u;
-    s->wf_fused = WF_FUSED_DEFAULT != 0;
-    if (const char* e = getenv("TRAYHIP_WF_FUSED")) s->wf_fused = atoi(e) != 0;
+    s->wf_bin_stages = tr_wfplan::bin_stages_wanted();
+    s->wf_fused = tr_wfplan::fused_wanted();
     if (const char* e = getenv("TRAYHIP_LEAN_TILES")) s->lean_tiles = atoi(e) != 0;   // (0: the base kernel, for A/B runs and bisecting)
     return TRAY_OK;
 }
@@ -793,32 +767,8 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
     };
     void* p = nullptr;
     w.n_chunks = n_slots / TR_BLOCK;
-    if (!grab((size_t)F_COUNT * n_slots * sizeof(float), &p)) return TRAY_E_NOMEM;
-    w.pool.data = static_cast<float*>(p); w.pool.n_slots = n_slots; w.pool.seg_cap = wf_seg_cap(w.n_chunks);
-    const size_t q_cap = (size_t)WF_SEGS * w.pool.seg_cap;   // entries of one queue: WF_SEGS segments (wavefront.h)
     const uint32_t n_chunks = w.n_chunks;                    // (lb_drop resets the fields on a failed grab)
-    if (!grab((size_t)n_chunks * sizeof(WfChunk), &p)) return TRAY_E_NOMEM;
-    w.d_chunks = static_cast<WfChunk*>(p);
-    if (!grab((size_t)n_chunks * ROWBIN_SIZE * sizeof(float), &p)) return TRAY_E_NOMEM;
-    w.d_bins = static_cast<float*>(p);
-    if (hipMemset(w.d_bins, 0, (size_t)n_chunks * ROWBIN_SIZE * sizeof(float)) != hipSuccess) { set_error("hipMemset of the row bins failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_DEVICE; }
-    if (!grab(2 * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    w.d_wf_counters = static_cast<uint32_t*>(p);
-    // ray queues A, B, C, regeneration queue and the control words of their segments, for up to WF_PIPES_MAX views (a view's segments
-    // are sized for its own chunks: WF_SEGS * TR_BLOCK entries of rounding per view and queue)
-    const size_t q_slack = (size_t)WF_PIPES_MAX * WF_SEGS * TR_BLOCK;
-    // (an entry of a ray queue is the ray: WF_RAY_WORDS words; the regeneration queue holds slot indices)
-    if (!grab(((3 * WF_RAY_WORDS + 1) * (q_cap + q_slack) + (size_t)WF_PIPES_MAX * WF_QCTL_WORDS) * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    w.d_queues = static_cast<uint32_t*>(p);
-    // ray binning: per view and stage (A, B) the histogram and the cursors of every segment's bins
-    if (!grab((size_t)WF_PIPES_MAX * 2u * 2u * WF_SEGS * WF_BINS * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    w.d_bin_ctl = static_cast<uint32_t*>(p);
-    w.wf_sort = !(s->feat & FEAT_TEX);   // the kind-pure kernels read lobes from the material table; textured materials have theirs per hit
-    if (w.wf_sort) {   // shading queues of the material sort (slot indices), one per material kind
-        if (!grab((size_t)WF_MAT_KINDS * (q_cap + q_slack) * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-        w.d_kind_queues = static_cast<uint32_t*>(p);
-    }
-    {
+    {   // the dynamic-fetch traversal's stacks and grid, then the shape of the queues and overflow columns they and the pool ask for (wavefront_plan.h)
         int per_cu = 0, cus = 256;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
@@ -833,20 +783,38 @@ static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 0>, TR_BLOCK, w.trace_lds_bytes);
         if (oe != hipSuccess || per_cu < 1) per_cu = 1;
         w.n_blocks_trace = (uint32_t)(cus * per_cu);
-        const size_t ovf_entries = (size_t)(full_depth - lds_depth + 1u) * w.n_blocks_trace * TR_BLOCK;   // per view: their traversal kernels overlap
-        w.ovf_entries = ovf_entries;
-        if (!grab((size_t)WF_PIPES_MAX * ovf_entries * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-        w.d_stack_overflow = static_cast<uint32_t*>(p);
+        w.lay = tr_wfplan::layout(n_chunks, full_depth, lds_depth, w.n_blocks_trace);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] dynamic-fetch traversal: %u of %u stack entries in LDS, %d workgroups per CU\n", lds_depth, full_depth, per_cu);
     }
+    const tr_wfplan::Layout lay = w.lay;
+    if (!grab((size_t)F_COUNT * n_slots * sizeof(float), &p)) return TRAY_E_NOMEM;
+    w.pool.data = static_cast<float*>(p); w.pool.n_slots = n_slots; w.pool.seg_cap = wf_seg_cap(n_chunks);
+    if (!grab((size_t)n_chunks * sizeof(WfChunk), &p)) return TRAY_E_NOMEM;
+    w.d_chunks = static_cast<WfChunk*>(p);
+    if (!grab((size_t)n_chunks * ROWBIN_SIZE * sizeof(float), &p)) return TRAY_E_NOMEM;
+    w.d_bins = static_cast<float*>(p);
+    if (hipMemset(w.d_bins, 0, (size_t)n_chunks * ROWBIN_SIZE * sizeof(float)) != hipSuccess) { set_error("hipMemset of the row bins failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_DEVICE; }
+    if (!grab(2 * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
+    w.d_wf_counters = static_cast<uint32_t*>(p);
+    if (!grab((size_t)lay.queue_bytes, &p)) return TRAY_E_NOMEM;   // ray queues A, B, C, regeneration queue and the views' control words
+    w.d_queues = static_cast<uint32_t*>(p);
+    if (!grab((size_t)lay.bin_ctl_bytes, &p)) return TRAY_E_NOMEM;
+    w.d_bin_ctl = static_cast<uint32_t*>(p);
+    w.wf_sort = !(s->feat & FEAT_TEX);   // the kind-pure kernels read lobes from the material table; textured materials have theirs per hit
+    if (w.wf_sort) {   // shading queues of the material sort
+        if (!grab((size_t)lay.kind_bytes, &p)) return TRAY_E_NOMEM;
+        w.d_kind_queues = static_cast<uint32_t*>(p);
+    }
+    if (!grab((size_t)lay.ovf_bytes, &p)) return TRAY_E_NOMEM;
+    w.d_stack_overflow = static_cast<uint32_t*>(p);
     if (hipHostMalloc(reinterpret_cast<void**>(&w.h_done), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("hipHostMalloc failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_NOMEM; }
     w.stack_bytes = s->stack_bytes; w.quad_stack_words = s->quad_stack_words; w.animated = s->animated;
     w.ready = true;
     return TRAY_OK;
 }
 
-// Wavefront schedule: rounds of six stage kernels over the path pool until every tile is done.
-// The host only polls a "tiles done" word every WF_POLL rounds; kernels of finished chunks exit at once.
+// Wavefront schedule: rounds of six stage kernels over the path pool until every tile is done. The views, a round's launches and the loop are
+// wavefront_plan.h's; what is this function's own: the streams and events of the views, their fork and join, the poll, the timing and the last_* fields.
 static int launch_wavefront(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                             uint32_t spp, uint32_t kf, float* rgbw_dev, hipStream_t stream, uint32_t smp_begin, uint32_t smp_end) {
     const WfBuffers& w = s->lb.wf;
@@ -861,81 +829,56 @@ static int launch_wavefront(TrayDeviceScene* s, const uint2* tiles, uint32_t til
         HIP_CHECK(hipStreamSynchronize(stream));   // `init` is pageable host memory
     }
     if (!s->accumulate) HIP_CHECK(hipEventRecord(s->ev0, stream));
-    uint32_t launches = 0;
-    // the views: equal shares of the chunks in use. Measured on the C5 stand-in at full detail (1 / 2 / 3 / 4 views): see DESIGN.md section 4
-    // (with rounds of 24 M slots and more one view is ahead: C5 stand-in 155.8 against 152.9 Msamples/s at 32 M; at 16 M two views 146.8 against 144.3)
-    uint32_t n_views = n_chunks >= (24u << 20) / TR_BLOCK ? 1u : 2u;
-    if (s->wf_req_views) n_views = std::min<uint32_t>(WF_PIPES_MAX, s->wf_req_views);   // tray_scene_set_wavefront
-    if (const char* e = getenv("TRAYHIP_WF_PIPES")) n_views = (uint32_t)std::max(1, std::min(WF_PIPES_MAX, atoi(e)));
-    n_views = std::max(1u, std::min(n_views, n_chunks / WF_SEGS));   // (a view of a few chunks would only add launches)
+    const uint32_t n_views = tr_wfplan::view_count(n_chunks, s->wf_req_views);
     s->last_views = n_views; s->last_slices = 1u << slice_shift; s->last_was_wavefront = true;
-    WfView views[WF_PIPES_MAX];
-    {
-        const size_t q_total = (size_t)WF_SEGS * w.pool.seg_cap + (size_t)WF_PIPES_MAX * WF_SEGS * TR_BLOCK;   // entries of one queue kind over all views
-        uint32_t* const qbase[4] = {w.d_queues, w.d_queues + WF_RAY_WORDS * q_total, w.d_queues + 2 * WF_RAY_WORDS * q_total, w.d_queues + 3 * WF_RAY_WORDS * q_total};
-        uint32_t* const qctl_base = qbase[3] + q_total;
-        size_t q_off = 0;
-        uint32_t c0 = 0;
-        for (uint32_t k = 0; k < n_views; ++k) {
-            const uint32_t c1 = (uint32_t)((uint64_t)n_chunks * (k + 1u) / n_views);
-            WfView& v = views[k];
-            v.n_chunks = c1 - c0;
-            v.dev = s->launch_dev;
-            if (v.dev.xf_cache && !v.dev.xf_table) v.dev.xf_cache += (size_t)c0 * TR_BLOCK * v.dev.n_moving * TR_XF_REC;   // [slot][moving instance][TR_XF_REC] (the table is indexed by time, not by slot)
-            v.pool = w.pool;
-            v.pool.first = c0 * TR_BLOCK;   // (the hit records are slot-major, the other fields field-major: the accessors add the view's first slot)
-            v.pool.seg_cap = wf_seg_cap(v.n_chunks);
-            v.chunks = w.d_chunks + c0;
-            v.bins = w.d_bins + (size_t)c0 * ROWBIN_SIZE;
-            v.qa = qbase[0] + WF_RAY_WORDS * q_off; v.qb = qbase[1] + WF_RAY_WORDS * q_off; v.qc = qbase[2] + WF_RAY_WORDS * q_off; v.qr = qbase[3] + q_off;
-            v.qctl = qctl_base + (size_t)k * WF_QCTL_WORDS;
-            v.kq = w.wf_sort ? w.d_kind_queues + (size_t)WF_MAT_KINDS * q_off : nullptr;
-            v.overflow = w.d_stack_overflow + (size_t)k * w.ovf_entries;
-            v.bin_ctl = w.d_bin_ctl ? w.d_bin_ctl + (size_t)k * 2u * 2u * WF_SEGS * WF_BINS : nullptr;
-            v.stream = stream;
-            if (k > 0) {
-                if (!s->wf_streams[k]) HIP_CHECK(hipStreamCreateWithFlags(&s->wf_streams[k], hipStreamNonBlocking));
-                if (!s->wf_join[k]) HIP_CHECK(hipEventCreateWithFlags(&s->wf_join[k], hipEventDisableTiming));
-                v.stream = s->wf_streams[k];
-            }
-            q_off += (size_t)WF_SEGS * v.pool.seg_cap;
-            c0 = c1;
-        }
-        if (n_views > 1u) {   // the other views start after what this call has put on the caller's stream so far
-            if (!s->wf_fork) HIP_CHECK(hipEventCreateWithFlags(&s->wf_fork, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(s->wf_fork, stream));
-            for (uint32_t k = 1; k < n_views; ++k) HIP_CHECK(hipStreamWaitEvent(views[k].stream, s->wf_fork, 0));
+    const WfLaunch args{tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift, smp_begin, smp_end};
+    WfOps views[WF_PIPES_MAX];
+    for (uint32_t k = 0; k < n_views; ++k) {
+        const tr_wfplan::View pv = tr_wfplan::view(w.lay, k, n_views, n_chunks);
+        WfOps& v = views[k];
+        v.s = s; v.a = &args;
+        v.n_chunks = pv.n_chunks;
+        v.dev = s->launch_dev;
+        if (v.dev.xf_cache && !v.dev.xf_table) v.dev.xf_cache += (size_t)pv.first_chunk * TR_BLOCK * v.dev.n_moving * TR_XF_REC;   // [slot][moving instance][TR_XF_REC] (the table is indexed by time, not by slot)
+        v.pool = w.pool;
+        v.pool.first = pv.first_chunk * TR_BLOCK;   // (the hit records are slot-major, the other fields field-major: the accessors add the view's first slot)
+        v.pool.seg_cap = pv.seg_cap;
+        v.chunks = w.d_chunks + pv.first_chunk;
+        v.bins = w.d_bins + (size_t)pv.first_chunk * ROWBIN_SIZE;
+        v.b = tr_wfplan::buffers(w.lay, pv, w.d_queues, w.wf_sort ? w.d_kind_queues : nullptr, w.d_bin_ctl, w.d_stack_overflow);
+        v.stream = stream;
+        if (k > 0) {   // (view 0 runs on the caller's stream)
+            if (!s->wf_streams[k]) HIP_CHECK(hipStreamCreateWithFlags(&s->wf_streams[k], hipStreamNonBlocking));
+            if (!s->wf_join[k]) HIP_CHECK(hipEventCreateWithFlags(&s->wf_join[k], hipEventDisableTiming));
+            v.stream = s->wf_streams[k];
         }
     }
-    // every chunk needs at most (spp/4 rounded up) samples x (max_depth + 2) rounds per tile, plus one round per tile switch
-    const uint64_t tiles_per_chunk = (tile_count + n_chunks - 1) / n_chunks;
-    const uint64_t max_rounds = tiles_per_chunk * (((uint64_t)((n + (1u << slice_shift) - 1u) >> slice_shift) + 3) / 4 * ((WF_FOLD_C ? 2u : 1u) * s->dev.max_depth + 3) + 4) + 2 * WF_POLL;   // (WF_FOLD_C: a vertex with a stage C ray takes two rounds)
-    bool done = false;
-    for (uint32_t k = 0; k < n_views; ++k) HIP_CHECK(hipMemsetAsync(views[k].qctl, 0, WF_QCTL_WORDS * sizeof(uint32_t), views[k].stream));   // (later: inside wf_round)
-    for (uint32_t round = 0; !done; ++round) {
-        for (uint32_t k = 0; k < n_views; ++k) {
-            const WfView& v = views[k];
-            if (v.bin_ctl && s->wf_bin_stages) HIP_CHECK(hipMemsetAsync(v.bin_ctl, 0, (size_t)2u * 2u * WF_SEGS * WF_BINS * sizeof(uint32_t), v.stream));
-            if (s->animated) wf_round<1>(s, v, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift, smp_begin, smp_end);
-            else wf_round<0>(s, v, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, slice_shift, smp_begin, smp_end);
-            launches += (WF_FOLD_C ? 8 : 10) + ((s->wf_bin_stages & 1u) ? 2 : 0) + ((s->wf_bin_stages & 2u) ? 2 : 0);   // (nominal: a kind-pure launch per material kind present comes on top in both forms)
-        }
-        if (round % WF_POLL == WF_POLL - 1) {
-            HIP_CHECK(hipGetLastError());
-            for (uint32_t k = 1; k < n_views; ++k) HIP_CHECK(hipStreamSynchronize(views[k].stream));
-            HIP_CHECK(hipMemcpyAsync(w.h_done, w.d_wf_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_CHECK(hipStreamSynchronize(stream));
-            done = *w.h_done >= tile_count;
-        }
-        if (round > max_rounds) { set_error("wavefront schedule did not terminate"); return TRAY_E_DEVICE; }
+    if (n_views > 1u) {   // the other views start after what this call has put on the caller's stream so far
+        if (!s->wf_fork) HIP_CHECK(hipEventCreateWithFlags(&s->wf_fork, hipEventDisableTiming));
+        HIP_CHECK(hipEventRecord(s->wf_fork, stream));
+        for (uint32_t k = 1; k < n_views; ++k) HIP_CHECK(hipStreamWaitEvent(views[k].stream, s->wf_fork, 0));
     }
+    const tr_wfplan::RoundCfg cfg{w.wf_sort, s->wf_fused, s->wf_bin_stages, w.d_bin_ctl != nullptr, s->mat_kinds_present};
+    const uint64_t max_rounds = tr_wfplan::max_rounds(tile_count, n_chunks, n, slice_shift, s->dev.max_depth);
+    const auto poll = [&]() -> int {   // the "tiles done" word, once every view has drained
+        HIP_CHECK(hipGetLastError());
+        for (uint32_t k = 1; k < n_views; ++k) HIP_CHECK(hipStreamSynchronize(views[k].stream));
+        HIP_CHECK(hipMemcpyAsync(w.h_done, w.d_wf_counters + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        return *w.h_done >= tile_count ? 1 : 0;
+    };
+    uint64_t rounds = 0;
+    const tr_wfplan::Ended ended = s->animated ? tr_wfplan::run<1>(views, n_views, cfg, max_rounds, WF_POLL, poll, &rounds)
+                                               : tr_wfplan::run<0>(views, n_views, cfg, max_rounds, WF_POLL, poll, &rounds);
+    if (ended == tr_wfplan::kNotTerminated) { set_error("wavefront schedule did not terminate"); return TRAY_E_DEVICE; }
+    if (ended == tr_wfplan::kFailed) return TRAY_E_DEVICE;   // (the failed call has set the error)
     for (uint32_t k = 1; k < n_views; ++k) {   // (the polls above have synchronised them; this keeps the caller's stream ordered after them in any case)
         HIP_CHECK(hipEventRecord(s->wf_join[k], views[k].stream));
         HIP_CHECK(hipStreamWaitEvent(stream, s->wf_join[k], 0));
     }
     HIP_CHECK(hipEventRecord(s->ev1, stream));
     s->timing_valid = true;
-    s->launches = launches;
+    s->launches = (uint32_t)(rounds * n_views * tr_wfplan::nominal_launches(s->wf_bin_stages));
     return TRAY_OK;
 }
 

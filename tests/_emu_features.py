@@ -54,8 +54,9 @@ def denoise_lib():
 
 @functools.lru_cache(None)
 def guide_lib():
-    h = C.CDLL(E.build("libtrayemu_guide.so", "emu_guide.cpp", _hip("guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h")
-                       + [os.path.join(E.EMU_DIR, "emu_denoise.cpp")] + E.denoise_plan_deps()))
+    h = C.CDLL(E.build("libtrayemu_guide.so", "emu_guide.cpp", _hip("guide_kernels.h", "block_compact.h", "denoise_kernels.h", "dev_libm.h", "noise_kernels.h",
+                                                                    "noise_plan.h")
+                       + [os.path.join(E.EMU_DIR, f) for f in ("emu_denoise.cpp", "emu_noise.cpp", "noise_plan_record.h")] + E.denoise_plan_deps()))
     h.emu_guide_halves.restype = C.c_int
     h.emu_guide_halves.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]

@@ -13,6 +13,8 @@
  * FAKEHIP_TILE_KERNEL=1 a "range dev=.. begin=.. end=.." line goes in front of the tile kernel's "launch" line (tests/test_sample_ranges_stub.py).
  * FAKEHIP_LOG_MEM=1 adds a "malloc bytes=.. ptr=.." line per hipMalloc and a "memset ptr=.. value=.. bytes=.. stream=.." line per hipMemsetAsync
  * (tools/wf_stub_logs.py: a launch's whole host-side footprint, to compare two builds of the library).
+ * FAKEHIP_NOISE_KEEP="10,3" makes the stand-in tile compaction keep that many tiles round after round, so that a noise-target call runs its later
+ * rounds (tests/test_noise_plan_stub.py).
  * A new add-on library gets a branch of its own in hipLaunchKernel. tests/_stub.py builds and preloads this file. */
 #define _GNU_SOURCE
 #include <dlfcn.h>
@@ -120,6 +122,25 @@ hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** args, size_t sh
     }
     if (found && strstr(di.dli_fname, "libtrayhip_noise") != NULL) {
         logf_("noise dev=%d grid=%u block=%u kernel=%s", t_device, g.x, b.x, sym);
+        /* FAKEHIP_NOISE_KEEP="10,3": successive k_noise_compact launches (queue, active, n, list, list_q, count) answer with the first 10 tiles of
+         * the queue, then the first 3, then none -- which ends a noise-target call -- and then from the start again. Unset: the
+         * arguments are not touched (the count stays 0: a call ends after round 0). */
+        const char* keep = getenv("FAKEHIP_NOISE_KEEP");
+        if (keep && strstr(sym, "k_noise_compact") != NULL) {
+            static const char* next = NULL;
+            pthread_mutex_lock(&g_mu);
+            if (!next) next = keep;
+            char* end = NULL;
+            uint32_t m = (uint32_t)strtoul(next, &end, 10);
+            next = end != next && *end == ',' ? end + 1 : (end == next ? NULL : end);   /* (past the last number: "none" next time, then over) */
+            pthread_mutex_unlock(&g_mu);
+            const uint32_t n = *(uint32_t*)args[2];
+            const uint64_t* const queue = *(const uint64_t**)args[0];   /* (x, y) pairs of words */
+            uint64_t* const list = *(uint64_t**)args[3];
+            uint32_t* const list_q = *(uint32_t**)args[4];
+            for (uint32_t i = 0; i < m && i < n; ++i) { list[i] = queue[i]; list_q[i] = i; }
+            **(uint32_t**)args[5] = m;   /* (a number above n writes n entries and reports itself: the count a call must refuse) */
+        }
         return 0;
     }
     /* FAKEHIP_TILE_KERNEL=1: the launch is k_path_tiles(scene, tiles, tile_count, chunk, chunk_stride, spp, kf, slice_shift, rgbw, counter, stats)

@@ -183,6 +183,30 @@ def test_a_real_threshold(tmp_path):
     assert (out.view(np.uint32) == sep.view(np.uint32)).all(), "out_dev differs from a separate tray_denoise_device call"
 
 
+@pytest.mark.parametrize("rule", ["raw", "filtered"])
+def test_the_launches_are_the_plans(rule, tmp_path):
+    """the launches TrayKernelTiming counts are those the plan's schedule (noise_plan.h, through the recording Ops of tests/emu/noise_plan_record.h)
+    makes when its count reads are answered as this call's were: after the round to `taken` samples a tile is active iff its n_t is larger"""
+    import _noise_plan as NP   # (loads the emulation library of the guide kernels, which has the plan's exports)
+    w, h, lo, hi, thr = 64, 48, 8, 64, 0.2
+    scene, *_ = NT.load(scenes.cornell_box(w, h, hi), tmp_path)
+    hip = T.Hip(0, seed=5)
+    q = NT.queue(scene, 0)
+    if rule == "raw":
+        import test_gpu_noise_target as RAW
+        *_, smp, err, tim = RAW.noise_target(scene, hip, 0, lo, hi, thr)
+    else:
+        *_, smp, err, tim, _ = filtered_target(scene, hip, 0, lo, hi, thr, with_out=True)
+    script = [] if rule == "raw" else [len(G.block_list(q, None, w, h))]
+    for taken in (8, 16, 32, 64):
+        active = (smp > taken).astype(np.uint32)
+        script += [int(active.sum())] + ([] if rule == "raw" else [len(G.block_list(q, active, w, h))])
+    events, rc, launches = NP.record(rule == "filtered", True, w, h, len(q), len(q), lo, hi, script)   # (one launch per render: a static scene's tile kernel)
+    print(f"{rule}: samples per tile {np.unique(smp, return_counts=True)}, {tim.launches} launches, the plan's {launches}")
+    assert rc == 0 and tim.launches == launches
+    assert tim.samples == 64 * sum(a["n"] * (a["end"] - a["begin"]) for g, a in events if g == "render")   # the ranges the plan lists are the samples taken
+
+
 def test_background_tiles_stop_at_min_spp(tmp_path):
     """tiles farther than the reconstruction filter's radius plus the denoiser's window from any geometry see 0 in both films and in both
     halves: error 0, so they stop after round 0; tiles on the lit spheres take more samples"""

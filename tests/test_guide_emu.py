@@ -3,11 +3,14 @@
 tests/emu/emu_guide.cpp runs k_dn_filter_halves, k_guide_mark and k_guide_compact as SIMT fibers. Bars: each filtered half within 4 x the f32
 statement's distance from the f64 one on that half, plus 1e-7 (_denoise_ref.bar's rule); (fa + fb) * 0.5 equal to the emulated k_dn_filter's
 output bit for bit; with a block list, the listed blocks equal to the full run bit for bit and every other word untouched; the block list exactly
-numpy's. Then the rounds of tray_render_noise_target_filtered_device on films of the oracle, driven from Python over the emulated kernels: errors
-within 4 ulps of the numpy metric of the emulated halves, flags and lists exact, n_t the numpy rule's at thresholds no tile's f64 error lies
-within 1e-3 relative of, and the property the rule rests on: at 32 samples at least 90 % of the tiles have a smaller filtered than raw error."""
+numpy's. Then the rounds of tray_render_noise_target_filtered_device on films of the oracle: the library's schedule (noise_plan.h) over the emulated
+kernels, with a stand-in for the range launches, observed from Python whenever the host has read a round's counts: errors within 4 ulps of the
+numpy metric of the emulated halves, flags and lists exact, n_t the numpy rule's at thresholds no tile's f64 error lies within 1e-3 relative of,
+the final filter's output a tray_denoise_device call's. The raw rule's rounds (tray_render_noise_target_device) go through the same schedule. And
+the property the rule rests on: at 32 samples at least 90 % of the tiles have a smaller filtered than raw error."""
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -17,6 +20,7 @@ from tray_rust_amd import scenes
 import _denoise_ref as D
 import _emu_features as EF
 import _guide_ref as G
+import _noise_plan as NP
 import _noise_ref as N
 import _ranges as R
 from _emu_features import SENTINEL, guide_halves as run_halves
@@ -32,11 +36,6 @@ def guide():
 @pytest.fixture(scope="module")
 def denoise():
     return EF.denoise_lib()
-
-
-@pytest.fixture(scope="module")
-def noise():
-    return EF.noise_lib()
 
 
 SIZES = [(67, 45), (160, 96)]
@@ -120,7 +119,7 @@ R_, F_, K_ = 7, 3, 0.45
 
 @pytest.fixture(scope="module")
 def oracle_rounds(tmp_path_factory, built):
-    """per scene: the queue and, per round, the oracle's even / odd films as they stand after that round if every tile takes it"""
+    """per scene: the queue and the oracle's film of every sample range a call may render, by (begin, end): each round's two halves alone"""
     out = {}
     for name in ("cornell_box", "smallpt"):
         d = str(tmp_path_factory.mktemp("guide_" + name))
@@ -131,11 +130,11 @@ def oracle_rounds(tmp_path_factory, built):
         scene, *_ = T.Scene.load_file(p)
         flat = scene.flatten(0)
         queue = R.tile_queue(W, H)
-        ranges = []   # per round: the films of the round's two ranges alone
+        ranges = {}
         lo, hi = 0, MIN_SPP
         while hi <= MAX_SPP:
             mid = lo + (hi - lo) // 2
-            ranges.append((hi,) + tuple(R.oracle_range(flat, queue, rng, MAX_SPP, SEED)[0] for rng in ((lo, mid), (mid, hi))))
+            ranges.update({rng: R.oracle_range(flat, queue, rng, MAX_SPP, SEED)[0] for rng in ((lo, mid), (mid, hi))})
             lo, hi = hi, hi * 2
         out[name] = (queue, ranges)
     return out
@@ -148,56 +147,68 @@ def tile_mask(queue, sel):
     return m
 
 
-def drive_rounds(guide, noise, queue, ranges, threshold):
-    """tray_render_noise_target_filtered_device's rounds over the emulated kernels, every step checked against numpy as it goes. A round adds the
-    oracle's range films inside the active tiles (the splats across tile borders stay with the tile that took the sample only approximately so:
-    the stand-in is exact in what the rule reads, the films as they stand). Returns n_t and the last error per tile, the f64 numpy rule's n_t (None if it
-    kept other tiles in some round) and every f64 error it compared with the threshold."""
-    n = len(queue)
-    even, odd = np.zeros((H, W, 4), F32), np.zeros((H, W, 4), F32)
-    err = np.full(n, -1.0, F32); active = np.full(n, 7, np.uint32); samples = np.zeros(n, np.uint32)
-    want_nt, want_active, err64_seen = np.zeros(n, np.uint32), np.ones(n, bool), []
-    sel, agree = np.arange(n), True
-    blocks = run_block_list(guide, queue, None, W, H)
-    assert (blocks == G.block_list(queue, None, W, H)).all()
-    fa, fb = np.full((H, W, 4), np.nan, F32), np.full((H, W, 4), np.nan, F32)   # (stale pixels are never read: NaN would show)
-    for hi, r_even, r_odd in ranges:
-        m = tile_mask(queue, sel)
-        even[m] += r_even[m]; odd[m] += r_odd[m]
-        fa, fb = run_halves(guide, even, odd, R_, F_, K_, blocks=blocks, into=(fa, fb))
-        whole = run_halves(guide, even, odd, R_, F_, K_)
-        bm = G.block_mask(blocks, W, H)
-        assert m[bm].sum() == m.sum(), "an active tile outside the listed blocks"
-        assert all((a.view(np.uint32)[bm] == b.view(np.uint32)[bm]).all() for a, b in ((fa, whole[0]), (fb, whole[1])))
-        full = len(sel) == n
-        e_, a_, s_ = EF.noise_error(noise, fa, fb, queue[sel], None if full else sel, hi, MAX_SPP, threshold, n)
-        want = np.array([G.tile_error(fa, fb, t) for t in queue[sel]], F32)
-        N.assert_ulps(e_[sel], want, 4, f"round to {hi}")
-        with np.errstate(invalid="ignore"):
-            assert (a_[sel] == ((~(e_[sel] < threshold)) & (hi < MAX_SPP)).astype(np.uint32)).all()
-        assert (s_[sel] == hi).all()
-        err[sel], active[sel], samples[sel] = e_[sel], a_[sel], s_[sel]
-        # the numpy rule in f64, on the f64 halves of the same films
-        A64, wA, B64, wB = G.halves(even, odd, R_, F_, K_, np.float64)
+def assert_halves_over(guide, B, blocks, sel, queue):
+    """B.fa / B.fb equal the halves of B's films over the whole frame on the listed blocks, bit for bit, and the tiles queue[sel] lie inside those"""
+    m, bm = tile_mask(queue, sel), G.block_mask(blocks, W, H)
+    assert m[bm].sum() == m.sum(), "an active tile outside the listed blocks"
+    whole = run_halves(guide, B.even, B.odd, R_, F_, K_)
+    assert all((a.view(np.uint32)[bm] == b.view(np.uint32)[bm]).all() for a, b in ((B.fa, whole[0]), (B.fb, whole[1])))
+
+
+def f64_tile_errors(B, tiles, filtered):
+    """the numpy rule in f64: the tiles' errors on the f64 halves of B's films (the raw rule: on the films)"""
+    fa64, fb64 = B.even, B.odd
+    if filtered:
+        A64, wA, B64, wB = G.halves(B.even, B.odd, R_, F_, K_, np.float64)
         fa64, fb64 = np.concatenate([A64, wA[..., None]], -1), np.concatenate([B64, wB[..., None]], -1)
-        e64 = np.array([G.tile_error(fa64, fb64, t, np.float64) for t in queue[sel]])
+    return np.array([G.tile_error(fa64, fb64, t, np.float64) for t in tiles])
+
+
+def drive_rounds(guide, queue, ranges, threshold, filtered=True, with_out=False):
+    """One tray_render_noise_target_filtered_device call (filtered False: tray_render_noise_target_device, the error that of the films themselves) in
+    the emulation -- the library's schedule (noise_plan.h) over the emulated kernels --, every round checked against numpy when the host has read
+    its counts. The render stand-in adds the oracle's range films inside the listed tiles (the splats across tile borders stay with the tile that
+    took the sample only approximately so: the stand-in is exact in what the rule reads, the films as they stand). Returns n_t and the last error
+    per tile, the f64 numpy rule's n_t (None if it kept other tiles in some round), every f64 error it compared with the threshold, the buffers."""
+    n = len(queue)
+    want_nt, want_active, err64_seen = np.zeros(n, np.uint32), np.ones(n, bool), []
+    st = types.SimpleNamespace(sel=None, hi=0, blocks=None, agree=True, rounds=0)
+
+    def render(B, sel, begin, end, film):
+        m = tile_mask(queue, sel)
+        film[m] += ranges[begin, end][m]
+        st.sel, st.hi = sel, end
+
+    def after_read(B, first, n_words):
+        sel, hi, blocks = st.sel, st.hi, st.blocks
+        st.blocks = B.blocks[:int(B.counts[1])].copy() if filtered else None   # the list the next round filters over
+        if sel is None:   # nothing is rendered yet: the blocks of the whole queue, a read of one word
+            assert filtered and (first, n_words) == (1, 1) and np.array_equal(st.blocks, G.block_list(queue, None, W, H))
+            return
+        assert (first, n_words) == (0, 2 if filtered else 1), "a round reads its counts in one copy"
+        if filtered:
+            assert_halves_over(guide, B, blocks, sel, queue)
+        fe, fo = (B.fa, B.fb) if filtered else (B.even, B.odd)   # the two films the error is taken from
+        N.assert_ulps(B.err[sel], np.array([G.tile_error(fe, fo, t) for t in queue[sel]], F32), 4, f"round to {hi}")
+        with np.errstate(invalid="ignore"):
+            assert (B.active[sel] == ((~(B.err[sel] < threshold)) & (hi < MAX_SPP)).astype(np.uint32)).all()
+        assert (B.samples[sel] == hi).all()
+        rest = np.setdiff1d(np.arange(n), sel)   # (the tiles that stopped earlier keep what they had)
+        assert (B.active[rest] == 0).all() and (B.samples[rest] == want_nt[rest]).all()
+        e64 = f64_tile_errors(B, queue[sel], filtered)
         err64_seen.append(e64)
         want_nt[sel] = hi
-        still = np.zeros(n, bool); still[sel] = ~(e64 < threshold) & (hi < MAX_SPP)
-        want_active &= still
+        want_active[np.setdiff1d(np.arange(n), sel[~(e64 < threshold) & (hi < MAX_SPP)])] = False
         # the next lists
-        out_xy = np.full((n, 2), 0xFFFFFFFF, np.uint32); out_q = np.full(n, 0xFFFFFFFF, np.uint32); count = np.zeros(1, np.uint32)
-        q = np.ascontiguousarray(queue)
-        assert noise.emu_noise_compact(q.ctypes.data, active.ctypes.data, n, out_xy.ctypes.data, out_q.ctypes.data, count.ctypes.data) == 0
-        nxt = np.flatnonzero(active)
-        assert int(count[0]) == len(nxt) and (out_q[:len(nxt)] == nxt).all() and (out_xy[:len(nxt)] == queue[nxt]).all()
-        blocks = run_block_list(guide, queue, active, W, H)
-        assert (blocks == G.block_list(queue, active, W, H)).all()
-        agree = agree and np.array_equal(np.flatnonzero(want_active), nxt)   # (the f32 kernels and the f64 rule keep the same tiles)
-        if len(nxt) == 0:
-            break
-        sel = nxt
-    return samples, err, want_nt if agree else None, np.concatenate(err64_seen)
+        nxt = np.flatnonzero(B.active)
+        assert int(B.counts[0]) == len(nxt) and (B.list_q[:len(nxt)] == nxt).all() and (B.list[:len(nxt)] == queue[nxt]).all()
+        assert not filtered or np.array_equal(st.blocks, G.block_list(queue, B.active, W, H))
+        st.agree = st.agree and np.array_equal(np.flatnonzero(want_active), nxt)   # (the f32 kernels and the f64 rule keep the same tiles)
+        st.rounds += 1
+
+    rc, launches, B = NP.noise_target(queue, W, H, MIN_SPP, MAX_SPP, threshold, render, after_read, filt=(R_, F_, K_) if filtered else None, with_out=with_out)
+    assert rc == 0 and launches == NP.call_launches(filtered, with_out, st.rounds), (rc, launches, st.rounds)
+    return B.samples.copy(), B.err.copy(), want_nt if st.agree else None, np.concatenate(err64_seen), B
 
 
 # between 0.15 and 0.3, where the filtered tile errors of these films lie (median 0.07 ... 0.14, largest 0.14 ... 0.41 over the rounds); chosen so that
@@ -206,12 +217,14 @@ THRESHOLDS = {"cornell_box": [0.17, 0.22, 0.27], "smallpt": [0.17, 0.22, 0.27]}
 
 
 @pytest.mark.parametrize("name", ["cornell_box", "smallpt"])
-def test_rounds_on_oracle_films(guide, noise, oracle_rounds, name):
+def test_rounds_on_oracle_films(guide, oracle_rounds, name):
     queue, ranges = oracle_rounds[name]
     counts = []
     for thr in THRESHOLDS[name]:
         assert 0.15 <= thr <= 0.3
-        samples, err, want_nt, e64 = drive_rounds(guide, noise, queue, ranges, F32(thr))
+        samples, err, want_nt, e64, B = drive_rounds(guide, queue, ranges, F32(thr), with_out=thr == THRESHOLDS[name][-1])
+        if B.out is not None:   # the final filter of the films as the call leaves them: a tray_denoise_device call's output
+            assert (B.out.view(np.uint32) == EF.denoise(EF.denoise_lib(), B.even, B.odd, R_, F_, K_).view(np.uint32)).all()
         rel = np.abs(e64[np.isfinite(e64)] - float(F32(thr))) / float(F32(thr))
         assert rel.min() > 1e-3, f"{name}: a tile's f64 error lies within 1e-3 relative of the threshold {thr}: choose another"
         assert want_nt is not None and (samples == want_nt).all(), "n_t is not the numpy rule's"
@@ -221,15 +234,35 @@ def test_rounds_on_oracle_films(guide, noise, oracle_rounds, name):
     assert counts[0] >= counts[1] >= counts[2] and counts[0] > counts[2], counts   # a tighter threshold takes more samples
 
 
+# the raw rule over the same films: its tile errors are larger (median 0.32 ... 0.40, largest 0.64 ... 0.70 over the rounds). From a scan of 0.20 ... 0.65 in
+# steps of 0.01 with the f64 statement alone: the nearest f64 error lies 6.4e-3, 1.9e-2, 2.4e-2 relative away on cornell_box, 7.5e-3, 6.9e-3, 1.8e-2 on smallpt
+RAW_THRESHOLDS = {"cornell_box": [0.29, 0.41, 0.55], "smallpt": [0.22, 0.31, 0.48]}
+
+
+@pytest.mark.parametrize("name", ["cornell_box", "smallpt"])
+def test_rounds_of_the_raw_rule_on_oracle_films(guide, oracle_rounds, name):
+    """tray_render_noise_target_device through the same schedule: no block lists, one count word per round, the error of the films themselves"""
+    queue, ranges = oracle_rounds[name]
+    counts = []
+    for thr in RAW_THRESHOLDS[name]:
+        samples, err, want_nt, e64, _ = drive_rounds(guide, queue, ranges, F32(thr), filtered=False)
+        rel = np.abs(e64[np.isfinite(e64)] - float(F32(thr))) / float(F32(thr))
+        assert rel.min() > 1e-3, f"{name}: a tile's f64 error lies within 1e-3 relative of the threshold {thr}: choose another"
+        assert want_nt is not None and (samples == want_nt).all(), "n_t is not the numpy rule's"
+        assert ((samples >= MIN_SPP) & (samples <= MAX_SPP) & (samples & (samples - 1) == 0)).all()
+        counts.append(float(samples.mean()))
+        print(f"{name} threshold {thr}: mean n_t {samples.mean():.1f}, tiles at max_spp {int((samples == MAX_SPP).sum())} of {len(samples)}")
+    assert counts[0] > counts[1] > counts[2] > MIN_SPP, counts
+
+
 @pytest.mark.parametrize("name", ["cornell_box", "smallpt"])
 def test_the_filtered_error_is_below_the_raw_one_at_32_samples(guide, oracle_rounds, name):
     """the property the rule rests on: where the filter helps, the difference of the filtered halves is smaller than that of the films"""
     queue, ranges = oracle_rounds[name]
     even, odd = np.zeros((H, W, 4), F32), np.zeros((H, W, 4), F32)
-    for hi, r_even, r_odd in ranges:
-        even += r_even; odd += r_odd
-        if hi == 32:
-            break
+    for i, ((begin, end), film) in enumerate(ranges.items()):   # (in the fixture's order: a round's first half, for even, then its second, for odd)
+        if end <= 32:
+            (odd if i % 2 else even)[...] += film
     fa, fb = run_halves(guide, even, odd, R_, F_, K_)
     raw = np.array([N.numpy_tile_error(even, odd, t) for t in queue])
     filt = np.array([G.tile_error(fa, fb, t) for t in queue])

@@ -23,6 +23,7 @@
 #include "launch_rules.h"
 #include "scene_plan.h"
 #include "denoise_plan.h"
+#include "noise_plan.h"
 #include "wavefront_plan.h"   // (WF_PIPES_MAX, WF_POLL)
 
 
@@ -89,15 +90,12 @@ struct LaunchBuffers {
     bool last_used_table = false;        // the last launch read the table
     bool owns_any() const { return wf.ready || xf_cache || d_xf_table; }
 };
-// tray_render_noise_target_device's per-tile state, n_tiles entries each, in one allocation made on first use: the round's tile list (coordinates and
-// queue indices; the error kernel reads it before the compaction rewrites it, in stream order, so one list serves every round), the next-round flags,
-// the samples taken and the errors (by queue index), and the list's length; h_count is the pinned pair of words the host reads the round's counts into (the
-// tile list's length; behind it, for the filtered rule, the block list's)
+// tray_render_noise_target_device's per-tile state in one allocation made on first use, laid out by noise_plan.h's tile_layout(n_tiles): the round's tile
+// list (coordinates and queue indices; the error kernel reads it before the compaction rewrites it, in stream order, so one list serves every round), the
+// next-round flags, the samples taken and the errors (by queue index), and the list's length; h_count is the pinned pair of words the host reads the
+// round's counts through (the tile list's length; behind it, for the filtered rule, the block list's)
 struct NoiseBuffers {
     void* mem = nullptr;
-    uint2* list = nullptr;
-    uint32_t* list_q = nullptr, * active = nullptr, * samples = nullptr, * d_count = nullptr;
-    float* err = nullptr;
     uint32_t* h_count = nullptr;
 };
 struct TrayDeviceScene {
@@ -945,104 +943,70 @@ int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32
     return TRAY_OK;
 }
 
-// What the filtered stopping rule adds to a round (tray_render_noise_target_filtered_device): the filter's arguments and the private scratch layout
-// [filter records: 48 bytes per pixel | fa | fb: RGBW films | flags | list: one word per 32 x 16 block | counts: tiles, blocks, 2 words of padding]
-struct GuideRounds {
-    uint32_t radius, patch;
-    float k;
-    void* records;
-    float* fa, * fb;
-    uint32_t* flags, * list, * counts;
+// ---- the two noise-target calls. What each refuses, the layouts of the per-tile buffers and of the filtered rule's scratch, and the rounds with their
+// one host read each are noise_plan.h's, shared with the host emulation; here the plan's schedule runs with launch_tiles and the add-on libraries'
+// launch functions on the call's stream.
+
+namespace nt = tr_ntplan;
+static_assert(nt::kFinalFilterLaunches == tr_denoise::kLaunches && tr_dnplan::kPrepareLaunches == tr_denoise::kPrepareLaunches,
+              "the plan counts the launches of a group as its library does");
+static_assert(tr_guide::kBlockW == TRAY_DENOISE_BLOCK_W && tr_guide::kBlockH == TRAY_DENOISE_BLOCK_H, "the plan's blocks are the guide library's");
+
+struct NoiseOps {   // the launch groups of the plan's schedule
+    TrayDeviceScene* s;
+    hipStream_t stream;
+    uint64_t seed;
+    uint32_t max_spp, width, height;
+    static const uint2* xy(const void* tiles) { return static_cast<const uint2*>(tiles); }
+    int render(const void* list, uint32_t n, uint32_t begin, uint32_t end, float* film, uint32_t* launches) {
+        const int rc = launch_tiles(s, xy(list), n, n, 1u, max_spp, seed, film, stream, begin, end);
+        if (rc == TRAY_OK) *launches += s->launches;
+        return rc;
+    }
+    int block_list(const void* queue, const uint32_t* active, uint32_t n, uint32_t* flags, uint32_t* list, uint32_t* count) {
+        HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)nt::frame_blocks(width, height) * sizeof(uint32_t), stream));
+        tr_guide::mark(stream, xy(queue), active, n, width, height, flags);
+        tr_guide::compact(stream, flags, width, height, list, count);
+        return TRAY_OK;
+    }
+    int halves(const float* even, const float* odd, void* records, uint32_t radius, uint32_t patch, float k, const uint32_t* blocks, uint32_t n_blocks,
+               float* fa, float* fb) {
+        tr_denoise::prepare(stream, even, odd, width, height, records);
+        const uint32_t made = tr_guide::halves(stream, records, width, height, radius, patch, k, blocks, n_blocks, fa, fb);
+        if (tr_denoise::kPrepareLaunches + made != nt::halves_launches(n_blocks)) {   // (the plan counts this group without asking)
+            set_error("tray_render_noise_target_filtered_device: the halves made other launches than the plan counts"); return TRAY_E_DEVICE;
+        }
+        return TRAY_OK;
+    }
+    void error(const float* fe, const float* fo, const void* list, const uint32_t* list_q, uint32_t n, uint32_t taken, uint32_t max_spp_, float threshold,
+               float* err, uint32_t* active, uint32_t* samples) {
+        tr_noise::error(stream, fe, fo, width, height, xy(list), list_q, n, taken, max_spp_, threshold, err, active, samples);
+    }
+    void compact(const void* queue, const uint32_t* active, uint32_t n, void* list, uint32_t* list_q, uint32_t* count) {
+        tr_noise::compact(stream, xy(queue), active, n, static_cast<uint2*>(list), list_q, count);
+    }
+    int read(const uint32_t* counts, uint32_t n_words, uint32_t* host) {   // through the scene's pinned words
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(s->nt.h_count, counts, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        std::copy(s->nt.h_count, s->nt.h_count + n_words, host);
+        return TRAY_OK;
+    }
+    int final_filter(const float* even, const float* odd, uint32_t radius, uint32_t patch, float k, float* out, void* records) {
+        tr_denoise::denoise(stream, even, odd, width, height, radius, patch, k, out, records);
+        HIP_CHECK(hipGetLastError());
+        return TRAY_OK;
+    }
 };
-static uint64_t guide_scratch_bytes(uint32_t width, uint32_t height) {
-    if (width == 0u || height == 0u) return 0u;
-    return tr_dnplan::plain_layout(width, height).total + (uint64_t)width * height * 32u + (uint64_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height) * 8u + 16u;
-}
-static GuideRounds guide_layout(void* scratch, uint32_t width, uint32_t height, uint32_t radius, uint32_t patch, float k) {
-    const size_t px = (size_t)width * height, nb = (size_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height);
-    GuideRounds g{};
-    g.radius = radius; g.patch = patch; g.k = k;
-    g.records = scratch;
-    g.fa = reinterpret_cast<float*>(static_cast<char*>(scratch) + tr_dnplan::plain_layout(width, height).total);
-    g.fb = g.fa + 4u * px;
-    g.flags = reinterpret_cast<uint32_t*>(g.fb + 4u * px);
-    g.list = g.flags + nb;
-    g.counts = g.list + nb;
-    return g;
+
+static nt::Scene noise_scene(const TrayDeviceScene* s) {
+    return s ? nt::Scene{true, s->sampler_kind, s->broken, s->dev.width, s->dev.height} : nt::Scene{false, 0u, false, 0u, 0u};
 }
 
-// The next round's block list of the filtered rule: the blocks that hold a tile of queue[0, tile_count) whose flag is set (active == null: every
-// tile), in row-major order, their number into g.counts[1]. Two launches.
-static int guide_block_list(const GuideRounds& g, hipStream_t stream, const uint2* queue, const uint32_t* active, uint32_t tile_count, uint32_t width,
-                            uint32_t height) {
-    HIP_CHECK(hipMemsetAsync(g.flags, 0, (size_t)tr_guide::blocks_x(width) * tr_guide::blocks_y(height) * sizeof(uint32_t), stream));
-    tr_guide::mark(stream, queue, active, tile_count, width, height, g.flags);
-    tr_guide::compact(stream, g.flags, width, height, g.list, g.counts + 1);
-    return TRAY_OK;
-}
-
-// The rounds of tray_render_noise_target_device and tray_render_noise_target_filtered_device over queue[0, tile_count) (include/trayhip.h), with
-// s->accumulate set: round r renders [a, b) -- [0, min_spp), then [min_spp 2^(r-1), min_spp 2^r) -- of the active tiles, [a, m) into even and [m, b)
-// into odd, then k_noise_error writes every active tile's error, samples and flag, k_noise_compact the next list in queue order, and the host reads
-// its length once. With g (the filtered rule) the error kernel reads the filtered halves of the films as they stand, computed over the blocks that
-// hold an active tile, and the round also makes the next block list; the host reads both lengths in its one copy.
-static int noise_rounds(TrayDeviceScene* s, const uint2* queue, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold, uint64_t seed,
-                        float* even_dev, float* odd_dev, const GuideRounds* g, hipStream_t stream, uint32_t* launches) {
-    NoiseBuffers& b = s->nt;
-    const uint32_t width = s->dev.width, height = s->dev.height;
-    const uint2* list = queue;        // round 0: the whole range, queue index = list index
-    const uint32_t* list_q = nullptr;
-    uint32_t n_active = tile_count, n_blocks = 0u;
-    uint32_t* const d_counts = g ? g->counts : b.d_count;
-    if (g) {   // round 0's blocks: those that hold a tile of the range
-        const int rc = guide_block_list(*g, stream, queue, nullptr, tile_count, width, height);
-        if (rc != TRAY_OK) return rc;
-        *launches += 2u;
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(b.h_count + 1, d_counts + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        n_blocks = b.h_count[1];
-    }
-    for (uint32_t lo = 0u, hi = min_spp;; lo = hi, hi *= 2u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        int rc = launch_tiles(s, list, n_active, n_active, 1u, max_spp, seed, even_dev, stream, lo, mid);
-        if (rc != TRAY_OK) return rc;
-        *launches += s->launches;
-        rc = launch_tiles(s, list, n_active, n_active, 1u, max_spp, seed, odd_dev, stream, mid, hi);
-        if (rc != TRAY_OK) return rc;
-        *launches += s->launches;
-        const float* fe = even_dev, * fo = odd_dev;   // the two films the error is taken from
-        if (g) {
-            if (n_blocks > tr_guide::blocks_x(width) * tr_guide::blocks_y(height)) {
-                set_error("tray_render_noise_target_filtered_device: the block list is longer than the frame has blocks"); return TRAY_E_DEVICE;
-            }
-            tr_denoise::prepare(stream, even_dev, odd_dev, width, height, g->records);
-            *launches += tr_denoise::kPrepareLaunches + tr_guide::halves(stream, g->records, width, height, g->radius, g->patch, g->k, g->list, n_blocks, g->fa, g->fb);
-            fe = g->fa; fo = g->fb;
-        }
-        tr_noise::error(stream, fe, fo, width, height, list, list_q, n_active, hi, max_spp, threshold, b.err, b.active, b.samples);
-        tr_noise::compact(stream, queue, b.active, tile_count, b.list, b.list_q, d_counts);
-        *launches += 2u;
-        if (g) {
-            rc = guide_block_list(*g, stream, queue, b.active, tile_count, width, height);
-            if (rc != TRAY_OK) return rc;
-            *launches += 2u;
-        }
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(b.h_count, d_counts, (g ? 2u : 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        n_active = b.h_count[0];
-        n_blocks = b.h_count[1];
-        if (n_active > tile_count) { set_error("tray_render_noise_target_device: the compacted tile list is longer than the queue"); return TRAY_E_DEVICE; }
-        if (n_active == 0u || hi >= max_spp) return TRAY_OK;   // (at max_spp no flag is set: n_active is 0 there too)
-        list = b.list; list_q = b.list_q;
-    }
-}
-
-// The body of the two noise-target calls once their arguments are checked: the per-tile buffers on first use, the call's events and statistics, the
-// rounds, with g and out_dev the final filter of the films (tray_denoise_device's three launches), and the per-tile results.
+// The body of the two noise-target calls once their arguments are checked, what is HIP's of it: the per-tile buffers on first use, the call's events
+// and statistics around the plan's rounds (f: the filtered rule's), and the per-tile results.
 static int noise_target_call(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold, uint64_t seed,
-                             float* even_dev, float* odd_dev, const GuideRounds* g, float* out_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
+                             float* even_dev, float* odd_dev, const nt::Filter* f, uint32_t* tile_samples, float* tile_error, void* stream_) {
     tr_rules::clamp_tile_range(s->n_tiles, tile_start, tile_count);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HIP_CHECK(hipSetDevice(s->device));
@@ -1050,81 +1014,48 @@ static int noise_target_call(TrayDeviceScene* s, uint32_t tile_start, uint32_t t
     s->empty_launch = false;
     if (tile_count == 0) { std::fprintf(stderr, "Warning: This block queue is empty!\n"); s->empty_launch = true; return TRAY_OK; }   // block_queue.rs:42-44
     NoiseBuffers& b = s->nt;
-    if (!b.mem) {   // [list: uint2 | list_q | active | samples | err: u32 / f32 | count], n_tiles entries each
-        const size_t n = s->n_tiles;
-        HIP_CHECK(hipMalloc(&b.mem, n * (sizeof(uint2) + 4u * sizeof(uint32_t)) + sizeof(uint32_t)));
-        b.list = static_cast<uint2*>(b.mem);
-        b.list_q = reinterpret_cast<uint32_t*>(b.list + n);
-        b.active = b.list_q + n;
-        b.samples = b.active + n;
-        b.err = reinterpret_cast<float*>(b.samples + n);
-        b.d_count = reinterpret_cast<uint32_t*>(b.err + n);
-    }
+    const nt::TileLayout tl = nt::tile_layout(s->n_tiles);
+    if (!b.mem) HIP_CHECK(hipMalloc(&b.mem, (size_t)tl.total));
     if (!b.h_count) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.h_count), 2u * sizeof(uint32_t), hipHostMallocDefault));
-    b.h_count[0] = b.h_count[1] = 0u;
     HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));   // (the launches below add to them: s->accumulate)
     HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
     HIP_CHECK(hipEventRecord(s->ev0, stream));
     uint32_t launches = 0u;
+    NoiseOps ops{s, stream, seed, max_spp, s->dev.width, s->dev.height};
     s->accumulate = true;
-    const int rc = noise_rounds(s, s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, g, stream, &launches);
+    const nt::Refusal no = nt::run(ops, nt::Target{s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, even_dev, odd_dev, b.mem, s->n_tiles}, f, &launches);
     s->accumulate = false;
-    if (rc != TRAY_OK) { s->timing_valid = false; return rc; }
-    if (g && out_dev) {
-        tr_denoise::denoise(stream, even_dev, odd_dev, s->dev.width, s->dev.height, g->radius, g->patch, g->k, out_dev, g->records);
-        launches += tr_denoise::kLaunches;
-        HIP_CHECK(hipGetLastError());
+    if (no.rc != TRAY_OK) {   // (a failed call has set the error itself; the renders before it have set timing_valid)
+        if (!no.msg.empty()) set_error(no.msg);
+        s->timing_valid = false;
+        return no.rc;
     }
     HIP_CHECK(hipEventRecord(s->ev1, stream));
-    HIP_CHECK(hipMemcpyAsync(tile_samples, b.samples, (size_t)tile_count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_CHECK(hipMemcpyAsync(tile_error, b.err, (size_t)tile_count * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(tile_samples, nt::at(b.mem, tl.samples), (size_t)tile_count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(tile_error, nt::at(b.mem, tl.err), (size_t)tile_count * sizeof(float), hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     s->launches = launches;
     s->timing_valid = true;
     return TRAY_OK;
 }
 
-// the argument rules the two noise-target calls share; `who` names the call in the message
-static int noise_target_args(const char* who, TrayDeviceScene* s, uint32_t min_spp, uint32_t max_spp, float threshold, const float* even_dev,
-                             const float* odd_dev, const uint32_t* tile_samples, const float* tile_error) {
-    const std::string w(who);
-    if (!s || !even_dev || !odd_dev || !tile_samples || !tile_error) { set_error(w + ": null argument"); return TRAY_E_INVALID; }
-    auto pow2 = [](uint32_t v) { return v != 0u && (v & (v - 1u)) == 0u; };
-    if (!pow2(min_spp) || !pow2(max_spp) || min_spp < 2u || max_spp < min_spp) {
-        set_error(w + ": min_spp and max_spp must be powers of two with 2 <= min_spp <= max_spp"); return TRAY_E_INVALID;
-    }
-    if (!(threshold >= 0.0f)) { set_error(w + ": threshold must be >= 0 (and not NaN)"); return TRAY_E_INVALID; }
-    if (even_dev == odd_dev) { set_error(w + ": the even and odd films must be different buffers"); return TRAY_E_INVALID; }
-    if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY) { set_error(w + ": sample ranges exist for the LowDiscrepancy sampler only"); return TRAY_E_UNSUPPORTED; }
-    if (s->broken) { set_error("this device scene is unusable: a tray_scene_update_frame on it failed"); return TRAY_E_INVALID; }
-    return TRAY_OK;
-}
-
 int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
                                     uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
-    const int rc = noise_target_args("tray_render_noise_target_device", s, min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
-    if (rc != TRAY_OK) return rc;
-    return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, nullptr, nullptr, tile_samples, tile_error, stream_);
+    const nt::Refusal no = nt::target_rules("tray_render_noise_target_device", noise_scene(s), min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
+    if (no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
+    return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, nullptr, tile_samples, tile_error, stream_);
 }
 
-uint64_t tray_noise_target_filtered_scratch_bytes(uint32_t width, uint32_t height) { return guide_scratch_bytes(width, height); }
+uint64_t tray_noise_target_filtered_scratch_bytes(uint32_t width, uint32_t height) { return nt::filtered_scratch_bytes(width, height); }
 
 int tray_render_noise_target_filtered_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp, float threshold,
                                              uint64_t seed, float* even_dev, float* odd_dev, uint32_t radius, uint32_t patch, float k, float* out_dev,
                                              void* scratch_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
-    const char* const who = "tray_render_noise_target_filtered_device";
-    int rc = noise_target_args(who, s, min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
-    if (rc != TRAY_OK) return rc;
-    if (!scratch_dev) { set_error(std::string(who) + ": null argument"); return TRAY_E_INVALID; }
-    if (const tr_dnplan::Refusal no = tr_dnplan::filter_args(who, s->dev.width, s->dev.height, radius, patch, k); no.rc != TRAY_OK) {   // (the filter's own rules)
-        set_error(no.msg); return no.rc;
-    }
-    const void* const bufs[4] = {even_dev, odd_dev, scratch_dev, out_dev};
-    if (!tr_dnplan::distinct_aligned(bufs, out_dev ? 4u : 3u)) {
-        set_error(std::string(who) + ": the films, the output and the scratch buffer must be different buffers, 16-byte aligned"); return TRAY_E_INVALID;
-    }
-    const GuideRounds g = guide_layout(scratch_dev, s->dev.width, s->dev.height, radius, patch, k);
-    return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, &g, out_dev, tile_samples, tile_error, stream_);
+    const nt::Refusal no = nt::filtered_rules("tray_render_noise_target_filtered_device", noise_scene(s), min_spp, max_spp, threshold, even_dev, odd_dev, radius,
+                                              patch, k, out_dev, scratch_dev, tile_samples, tile_error);
+    if (no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
+    const nt::Filter f{radius, patch, k, scratch_dev, out_dev};
+    return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, &f, tile_samples, tile_error, stream_);
 }
 
 // ---- the thirteen tray_denoise_*_device calls. What each refuses, its scratch layout and its launches in order are denoise_plan.h's, shared with the

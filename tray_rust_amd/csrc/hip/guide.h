@@ -4,7 +4,8 @@
 #pragma once
 
 namespace tr_guide {
-// 32 x 16 pixel blocks of a width x height frame (k_dn_filter's tiles)
+// 32 x 16 pixel blocks of a width x height frame (k_dn_filter's tiles; guide.hip checks the two constants against the kernels')
+constexpr uint32_t kBlockW = 32u, kBlockH = 16u;
 uint32_t blocks_x(uint32_t width);
 uint32_t blocks_y(uint32_t height);
 // fa / fb = the cross-filtered halves of the prepared scratch (tr_denoise::prepare), over the n_blocks blocks of `blocks`, or over every block

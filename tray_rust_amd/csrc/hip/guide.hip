@@ -8,6 +8,7 @@
 
 namespace tr_guide {
 
+static_assert(kBlockW == DN_TW && kBlockH == DN_TH, "guide.h states k_dn_filter's tile");
 uint32_t blocks_x(uint32_t width) { return tr_denoise::dn_tiles_x(width); }
 uint32_t blocks_y(uint32_t height) { return tr_denoise::dn_tiles_y(height); }
 

@@ -20,9 +20,10 @@ def _stale(so, deps):
 
 
 def device_deps():
-    """what emu_kernels.cpp is compiled from besides itself: the shim, the wavefront plan's recording Ops, every device source and header (the host-only
-    plans among them), and the two headers they share with the host"""
-    deps = [os.path.join(EMU_DIR, "hip_emu.h"), os.path.join(EMU_DIR, "wavefront_plan_record.h")] + [os.path.join(HIP_DIR, f) for f in os.listdir(HIP_DIR) if f.endswith((".h", ".hip"))]
+    """what emu_kernels.cpp is compiled from besides itself: the shim, the wavefront plan's recording Ops and the launch-buffer plan's scripted Ops, every
+    device source and header (the host-only plans among them), and the two headers they share with the host"""
+    deps = [os.path.join(EMU_DIR, f) for f in ("hip_emu.h", "wavefront_plan_record.h", "launch_buffers_plan_record.h")]
+    deps += [os.path.join(HIP_DIR, f) for f in os.listdir(HIP_DIR) if f.endswith((".h", ".hip"))]
     return deps + [os.path.join(ROOT, "tray_rust_amd", "csrc", "host", "gates.hpp"), os.path.join(ROOT, "include", "trayhip.h")]
 
 

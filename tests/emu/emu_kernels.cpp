@@ -84,6 +84,8 @@ NOINSTR int emu_profile_dump(const char* path) {
 #include "../../tray_rust_amd/csrc/hip/scene_plan.h"      // ... its per-scene decisions ...
 #include "../../tray_rust_amd/csrc/hip/wavefront_plan.h"  // ... and its wavefront schedule: the emulation applies them, it has no copy
 #include "wavefront_plan_record.h"                        // (tests/test_wavefront_plan.py's exports)
+#include "../../tray_rust_amd/csrc/hip/launch_buffers_plan.h"   // the library's launch-buffer plan, which the emulation does not run: its own buffers are vectors
+#include "launch_buffers_plan_record.h"                   // (tests/test_launch_buffers_plan.py's exports)
 #ifdef TR_SAMPLE_RANGES   // (emu_sample_ranges.cpp) the kernels take a sample range: EMU_RANGE appends it to a call, and only there do the two builds differ
 #define EMU_RANGE(...) , __VA_ARGS__
 #else
@@ -388,7 +390,7 @@ int emu_wf_trace(const TrayFlatScene* f, int stage, uint32_t n, const TrayRay* r
     return 0;
 }
 
-// TRAYHIP_EMU_XF_TABLE=1: the frame's transform table (device_api.hip: xf_table_ensure, k_xf_table_build) under the emulated kernels. The table of all
+// TRAYHIP_EMU_XF_TABLE=1: the frame's transform table (launch_buffers_plan.h: table_ensure; k_xf_table_build) under the emulated kernels. The table of all
 // 2^24 shutter-time indices is 2 GB per moving instance: here it is a sparse mapping whose records exist for the indices the rendered (pixel, sample)
 // pairs draw -- evaluated with k_xf_table_build's expressions --, which are the only ones the kernels read.
 struct SparseXfTable {
@@ -509,7 +511,7 @@ static int render_wavefront(const TrayFlatScene* f, const uint32_t* tiles_xy, ui
         xf_cache.assign((size_t)n_moving * TR_XF_REC * n_slots, 0.0f);
         e.d.xf_cache = xf_cache.data(); e.d.moving_ids = moving_ids.data(); e.d.n_moving = n_moving; e.d.xf_stride = n_moving; e.d.xf_cache_lanes = n_slots; e.d.xf_aos = 1u;
     }
-    SparseXfTable table;   // TRAYHIP_EMU_XF_TABLE=1: the stage kernels index the frame's table by the path's time index (device_api.hip: launch_prepare's wavefront branch)
+    SparseXfTable table;   // TRAYHIP_EMU_XF_TABLE=1: the stage kernels index the frame's table by the path's time index (device_api.hip: fill_launch_dev's wavefront branch)
     if (moving && getenv("TRAYHIP_EMU_XF_TABLE") && atoi(getenv("TRAYHIP_EMU_XF_TABLE")) != 0) {
         if (!table.build(f, e.d.frame, moving_ids.data(), n_moving, tiles_xy, tile_count, spp, seed)) return -5;
         if (table.data) {

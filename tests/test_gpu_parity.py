@@ -442,6 +442,43 @@ def test_a_frame_sequence_keeps_its_pool_and_its_table_buffer(tmp_path, monkeypa
     assert rmse(rt.get_renderf32().reshape(rt.height, rt.width, 4), cpu) < 1e-5
 
 
+def test_a_pool_sized_for_a_table_launch_gets_a_cache_for_every_slot(tmp_path, monkeypatch):
+    """ADVICE round 6, second finding (sequence "a" of tests/_launch_buffer_sequences.py, here with kernels that run): a per-path launch leaves a cache of
+    32 768 lanes, tray_scene_set_wavefront frees the pool, a table launch allocates a pool of up to 131 072 slots, the table goes off -- the stage kernels
+    of the next launch index the per-path cache by pool slot, so it must have a record for every slot, and every launch renders the oracle's frame."""
+    TR_XF_REC = 32   # floats per record of the cache and the table (dev_anim.h)
+    monkeypatch.setenv("TRAYHIP_MODE", "wave")
+    monkeypatch.setenv("TRAYHIP_XF_CACHE_BYTES", str(4 * TR_XF_REC * 4 * 32768))   # a cache budget of 32 768 lanes for the four moving instances
+    monkeypatch.delenv("TRAYHIP_WF_SLOTS", raising=False)
+    scene, rt, _, fi = T.Scene.load_file(scenes.write_moving_box(str(tmp_path), width=64, height=64, samples=16))
+    hip = T.Hip(0, seed=4)
+    scene.device_scene(0, 0)
+    cpu, st = O.render_tiles(scene.flatten(0), 16, seed=4)
+    images = []
+
+    def launch(table):
+        hip.set_transform_table(scene, table)
+        rt.clear()
+        hip.render(scene, rt, _config_at(fi, 0, 16))
+        sch = hip.schedule(scene)
+        assert sch["launched_wavefront"] == 1 and sch["transform_table"] == table
+        if not table:
+            assert sch["xf_cache_bytes"] >= sch["pool_slots"] * sch["n_moving"] * TR_XF_REC * 4 > 0, sch
+        images.append(rt.get_renderf32().reshape(rt.height, rt.width, 4).copy())
+        assert hip.last_timing.samples == st.samples and int(hip.last_timing.vertices) == int(st.vertices)
+        assert rmse(images[-1], cpu) < 1e-5
+        assert np.abs(images[-1] - images[0]).max() <= 2e-5 * max(1.0, float(np.abs(images[0]).max()))
+        return sch
+
+    small = launch(0)
+    assert small["pool_slots"] == 32768
+    hip.set_wavefront(scene, 131072)
+    assert hip.schedule(scene)["pool_slots"] == 0
+    large = launch(1)
+    assert large["pool_slots"] > small["pool_slots"]
+    assert launch(0)["pool_slots"] == large["pool_slots"]
+
+
 # ---- moving scenes (SURVEY 8f rank 1): per-ray spline evaluation, animated emission and camera ----
 @pytest.fixture(scope="module")
 def moving(tmp_path_factory):

@@ -25,6 +25,7 @@
 #include "denoise_plan.h"
 #include "noise_plan.h"
 #include "wavefront_plan.h"   // (WF_PIPES_MAX, WF_POLL)
+#include "launch_buffers_plan.h"
 
 
 struct TrayDevBuf { const char* key; void* ptr; size_t bytes; };
@@ -54,11 +55,10 @@ static TraySceneIdentity scene_identity(const TrayFlatScene* f) {
     return id;
 }
 // The three large buffers of a device scene's launches -- the wavefront pool with its queues, chunk records, row bins and overflow stacks; the per-path
-// transform cache; the frame's transform table (dev_geom.h: xf_time_index) -- and what they were sized for. lb_drop frees any of them, a frame update
-// moves them to the next frame's scene and lb_fit drops what it cannot use, launch_prepare picks cache or table per launch and sizes the pool.
-struct WfBuffers {   // the wavefront schedule's pool and the buffers that go with it (wf_alloc; 0.47 KB per slot)
+// transform cache; the frame's transform table (dev_geom.h: xf_time_index). What they were sized for, and every decision to keep, drop or allocate one, is
+// launch_buffers_plan.h's (st); LbOps below makes the HIP calls for it.
+struct WfBuffers {   // the wavefront schedule's pool and the buffers that go with it (LbOps::grant_pool; 0.47 KB per slot)
     WfPool pool{nullptr, 0};
-    bool ready = false;                  // every buffer below exists (a failed allocation leaves this false)
     WfChunk* d_chunks = nullptr;         // n_chunks of them, and as many row bins
     float* d_bins = nullptr;
     uint32_t n_chunks = 0;
@@ -71,24 +71,15 @@ struct WfBuffers {   // the wavefront schedule's pool and the buffers that go wi
     uint32_t n_blocks_trace = 0;         // persistent grid of k_wf_trace_dyn
     uint32_t trace_lds_depth = 0, trace_lds_bytes = 0;   // LDS part of the dynamic-fetch kernel's stacks; deeper entries go to d_stack_overflow
     bool wf_sort = true;                 // material sort of the shading stage (k_wf_begin's LDS counting sort -> k_wf_query_kind); off for textured scenes
-    uint32_t stack_bytes = 0, quad_stack_words = 0;   // the scene's traversal stacks and ...
-    bool animated = false;               // ... kernels the buffers were sized for
     std::vector<void*> allocs;           // the device buffers above
 };
 struct LaunchBuffers {
-    bool wavefront = false;              // the schedule the cache's layout and the pool were made for
+    tr_lbplan::State st;                 // which of the three exist, what they were sized for, what the last launch read
     WfBuffers wf;
-    bool wf_shrunk = false;              // the pool came out smaller than asked for (allocation failed, halved): frame updates keep it
-    // the per-path transform cache (wavefront: one record of TR_XF_REC floats per pool slot and moving instance; tile kernel: one column per resident thread)
-    float* xf_cache = nullptr; size_t xf_cache_bytes = 0;
-    uint32_t xf_cache_lanes = 0;         // paths the cache has room for; for a wavefront cache that does not exist yet: its budget (lb_fit)
+    float* xf_cache = nullptr;           // the per-path transform cache (wavefront: one record of TR_XF_REC floats per pool slot and moving instance; tile kernel: one column per resident thread)
     float* d_xf_table = nullptr;         // the frame's transform table, built by the first launch that wants it
-    uint32_t xf_table_stride = 0, xf_table_cap = 0;   // records per time index in use / room for (the next frames of a sequence may move more instances)
-    bool xf_table_built = false;         // ... for THIS frame (a frame update hands the buffer on, the frame's first launch that wants the table builds it)
     hipEvent_t xf_table_ev = nullptr;    // recorded behind k_xf_table_build on xf_table_stream: a launch of the frame on ANOTHER stream waits for it
     hipStream_t xf_table_stream = nullptr;
-    bool last_used_table = false;        // the last launch read the table
-    bool owns_any() const { return wf.ready || xf_cache || d_xf_table; }
 };
 // tray_render_noise_target_device's per-tile state in one allocation made on first use, laid out by noise_plan.h's tile_layout(n_tiles): the round's tile
 // list (coordinates and queue indices; the error kernel reads it before the compaction rewrites it, in stream order, so one list serves every round), the
@@ -132,7 +123,7 @@ struct TrayDeviceScene {
     uint32_t quad_stack_words = 0;         // stack words per lane the wavefront traversal needs for this frame's trees
     bool narrow_trees = true;         // every node's offset fits a descriptor (host/gates.hpp): the wavefront traversal keeps nodes as descriptors
     bool ordered_boxes = true;        // every BVH box has min <= max (host/gates.hpp: QuadTrees::ordered)
-    DevScene launch_dev{};               // what the kernels of the current render call get: `dev` with the transform cache, or the table in its place (launch_prepare)
+    DevScene launch_dev{};               // what the kernels of the current render call get: `dev` with the transform cache, or the table in its place (fill_launch_dev)
     bool camera_animated = false;
     uint32_t xf_movable = 0;             // instances (+ camera) whose transform has a level of several keyframes: what ANY frame of the sequence can move
     int xf_table_req = -1;               // tray_scene_set_transform_table: -1 = by the launch's sample count, 0 = never, 1 = always
@@ -197,15 +188,6 @@ static int upload(TrayDeviceScene* s, const char* key, bool unchanged, const T* 
 }
 
 
-#ifndef WF_SLOTS
-// Path pool slots the schedule asks for (capped by the film: a chunk of 256 per tile slice, 16 slices per tile -- 132.7 M at 1080p -- and by a third of the
-// free memory; 0.47 KB per slot with queues and bins: 62 GB for a 1080p film on a 288 GB part). Every stage kernel ends with the tail of its slowest rays,
-// and fewer, larger rounds pay it less often: 78 / 106 / 132 / 145 / 152 Msamples/s at 2 / 4 / 8 / 16 / 32 M slots (round 4); round 6, frame 64 / frame 127
-// of the C5 stand-in at 512 spp: 237.6 / 169.7 at 32 M (4 slices per tile), 250 - 253 / 174 - 175 at 64 M (8), 256.6 / 177.7 at 128 M (16) -- as long as the
-// pool's chunks and the work items are EQUAL in number (96 M slots under 16 slices: 242.0 / 170.5, a quarter of the chunks takes a second item while the others
-// idle): launch_wavefront cuts tiles until the items fill the chunks and no further (profiles/r06_c5_pool_64m.txt, r06_c5_pool_128m.txt).
-#define WF_SLOTS (128u << 20)
-#endif
 using tr_wfplan::QA; using tr_wfplan::QB; using tr_wfplan::QC; using tr_wfplan::QR; using tr_wfplan::Queue;
 // What every view of a wavefront launch renders: the arguments of launch_wavefront
 struct WfLaunch {
@@ -270,80 +252,143 @@ struct WfOps {
     }
 };
 
-// Path pool slots of the wavefront schedule: never more than the film has pixels x 4 x WF_MAX_SLICES (a chunk of 256 per tile slice), and for
-// moving scenes never more than the per-path transform cache (112 B per slot and instance that moves within the frame) can hold within two
-// fifths of the device's free memory; a few hundred thousand slots already fill the chip, but every stage kernel ends with the tail of its
-// slowest rays and fewer, larger rounds pay it less often
-// bytes of the schedule's buffers per pool slot (pool fields, three ray queues + regeneration queue, kind queues, fallback word, row bins per chunk)
-static size_t wf_bytes_per_slot() {
-    return (size_t)F_COUNT * sizeof(float) + (3 * WF_RAY_WORDS + 1) * sizeof(uint32_t) + WF_MAT_KINDS * sizeof(uint32_t) +
-           ((size_t)ROWBIN_SIZE * sizeof(float) + sizeof(WfChunk)) / TR_BLOCK;
+// the plain facts of the scene that launch_buffers_plan.h's rules are functions of
+static tr_lbplan::Facts lb_facts(const TrayDeviceScene* s) {
+    return tr_lbplan::Facts{s->n_tiles, (uint32_t)s->n_blocks, s->wavefront, s->animated, s->deferred_n_moving, s->stack_bytes, s->quad_stack_words,
+                            s->xf_movable, s->camera_animated, s->wf_req_slots, s->xf_table_req};
 }
-// what `req_slots` (tray_scene_set_wavefront; 0 = none), the environment or the default ask for, before memory is looked at
-static uint32_t wf_slot_wish(const TrayDeviceScene* s, uint32_t req_slots) {
-    uint32_t n_slots = WF_SLOTS;
-    if (req_slots) n_slots = std::max<uint32_t>(req_slots, 64u * TR_BLOCK) / TR_BLOCK * TR_BLOCK;   // tray_scene_set_wavefront
-    if (const char* e = getenv("TRAYHIP_WF_SLOTS")) n_slots = (uint32_t)std::max(256l, atol(e)) / TR_BLOCK * TR_BLOCK;
-    const uint64_t by_tiles = (uint64_t)std::max<uint32_t>(s->n_tiles, 1u) * TR_BLOCK * WF_MAX_SLICES;   // (a tile's samples can be cut into that many work items: launch_wavefront)
-    return (uint32_t)std::min<uint64_t>(n_slots, by_tiles);
-}
-static size_t device_free_bytes() {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)16 << 30; }
-    return free_b;
-}
-// `slots` within the share of the memory the pool may take, cut to the round-6 shape; free_b: what counts as free (hipMemGetInfo + what a frame update reclaims)
-static uint32_t wf_slot_fit(const TrayDeviceScene* s, uint64_t slots, size_t free_b, uint32_t req_slots) {
-    // the pool with its queues and bins (~0.47 KB per slot: 15 GB at 32 M) stays within a third of what is free now -- static scenes too
-    // (a host that keeps several device scenes gets pools that fit beside each other; launch_prepare halves on top if hipMalloc refuses)
-    {
-        const uint64_t fit = (uint64_t)free_b / 3u / wf_bytes_per_slot() / TR_BLOCK * TR_BLOCK;
-        slots = std::min<uint64_t>(slots, std::max<uint64_t>(fit, (uint64_t)64 * TR_BLOCK));
+// The Ops of launch_buffers_plan.h's procedures on a device scene: the HIP calls, the buffers' pointers, the error texts. stream: the launch's.
+struct LbOps {
+    TrayDeviceScene* s;
+    hipStream_t stream = nullptr;
+
+    bool free_bytes(uint64_t* out) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+        *out = free_b;
+        return true;
     }
-    // (round 6) the schedule is fastest with ONE work item per chunk (profiles/r06_c5_pool_128m.txt: 96 M slots under 16 slices per tile lose to 64 M under 8), so a
-    // pool that memory cut below the film's 16 slices per tile is cut further to the next tiles x 256 x 2^k below it -- never to less than one chunk per tile
-    {
-        const uint64_t per_tile_level = (uint64_t)std::max<uint32_t>(s->n_tiles, 1u) * TR_BLOCK;
-        if (slots > per_tile_level && !req_slots && !getenv("TRAYHIP_WF_SLOTS")) {
-            uint64_t fit = per_tile_level;
-            while (fit * 2u <= slots && fit * 2u <= per_tile_level * WF_MAX_SLICES) fit *= 2u;
-            slots = fit;
+    bool grant_cache(uint32_t lanes, uint64_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of the per-path transform cache failed: " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(s->deferred_n_moving) +
+                      " moving instances x " + std::to_string(lanes) + " paths (tray_scene_set_wavefront / TRAYHIP_WF_SLOTS / TRAYHIP_XF_CACHE_BYTES bound it)");
+            return false;
+        }
+        s->lb.xf_cache = static_cast<float*>(p);
+        return true;
+    }
+    bool grant_table(uint64_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        s->lb.d_xf_table = static_cast<float*>(p);
+        return true;
+    }
+    // every buffer of the wavefront schedule for a pool of n_slots; on failure nothing stays allocated and TRAY_E_NOMEM is returned
+    int grant_pool(uint32_t n_slots) {
+        WfBuffers& w = s->lb.wf;
+        auto grab = [&](uint64_t bytes, void** out) -> bool {
+            void* p = nullptr;
+            const hipError_t e = hipMalloc(&p, bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("hipMalloc of " + std::to_string(bytes >> 20) + " MiB failed: " + hipGetErrorString(e));
+                drop(tr_lbplan::kPool);
+                return false;
+            }
+            w.allocs.push_back(p);
+            *out = p;
+            return true;
+        };
+        void* p = nullptr;
+        w.n_chunks = n_slots / TR_BLOCK;
+        const uint32_t n_chunks = w.n_chunks;                    // (drop resets the fields on a failed grab)
+        {   // the dynamic-fetch traversal's stacks and grid, then the shape of the queues and overflow columns they and the pool ask for (wavefront_plan.h)
+            int per_cu = 0, cus = 256;
+            hipDeviceProp_t prop;
+            if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+            const uint32_t full_depth = tr_lbplan::trace_full_depth(s->quad_stack_words), lds_depth = tr_lbplan::trace_lds_depth(full_depth);
+            w.trace_lds_depth = lds_depth;
+            w.trace_lds_bytes = lds_depth * TR_BLOCK * (uint32_t)sizeof(uint32_t);
+            hipError_t oe = s->animated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 1>, TR_BLOCK, w.trace_lds_bytes)
+                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 0>, TR_BLOCK, w.trace_lds_bytes);
+            if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+            w.n_blocks_trace = (uint32_t)(cus * per_cu);
+            w.lay = tr_wfplan::layout(n_chunks, full_depth, lds_depth, w.n_blocks_trace);
+            if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] dynamic-fetch traversal: %u of %u stack entries in LDS, %d workgroups per CU\n", lds_depth, full_depth, per_cu);
+        }
+        const tr_wfplan::Layout lay = w.lay;
+        if (!grab(tr_lbplan::pool_bytes(n_slots), &p)) return TRAY_E_NOMEM;
+        w.pool.data = static_cast<float*>(p); w.pool.n_slots = n_slots; w.pool.seg_cap = wf_seg_cap(n_chunks);
+        if (!grab(tr_lbplan::chunk_bytes(n_chunks), &p)) return TRAY_E_NOMEM;
+        w.d_chunks = static_cast<WfChunk*>(p);
+        if (!grab(tr_lbplan::bin_bytes(n_chunks), &p)) return TRAY_E_NOMEM;
+        w.d_bins = static_cast<float*>(p);
+        if (hipMemset(w.d_bins, 0, tr_lbplan::bin_bytes(n_chunks)) != hipSuccess) { set_error("hipMemset of the row bins failed"); drop(tr_lbplan::kPool); return TRAY_E_DEVICE; }
+        if (!grab(2 * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
+        w.d_wf_counters = static_cast<uint32_t*>(p);
+        if (!grab(lay.queue_bytes, &p)) return TRAY_E_NOMEM;   // ray queues A, B, C, regeneration queue and the views' control words
+        w.d_queues = static_cast<uint32_t*>(p);
+        if (!grab(lay.bin_ctl_bytes, &p)) return TRAY_E_NOMEM;
+        w.d_bin_ctl = static_cast<uint32_t*>(p);
+        w.wf_sort = !(s->feat & FEAT_TEX);   // the kind-pure kernels read lobes from the material table; textured materials have theirs per hit
+        if (w.wf_sort) {   // shading queues of the material sort
+            if (!grab(lay.kind_bytes, &p)) return TRAY_E_NOMEM;
+            w.d_kind_queues = static_cast<uint32_t*>(p);
+        }
+        if (!grab(lay.ovf_bytes, &p)) return TRAY_E_NOMEM;
+        w.d_stack_overflow = static_cast<uint32_t*>(p);
+        if (hipHostMalloc(reinterpret_cast<void**>(&w.h_done), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("hipHostMalloc failed"); drop(tr_lbplan::kPool); return TRAY_E_NOMEM; }
+        return TRAY_OK;
+    }
+    void drop(unsigned what) {
+        LaunchBuffers& b = s->lb;
+        if (what & tr_lbplan::kPool) {
+            for (void* p : b.wf.allocs) (void)hipFree(p);
+            if (b.wf.h_done) (void)hipHostFree(b.wf.h_done);
+            b.wf = WfBuffers{};
+        }
+        if (what & tr_lbplan::kCache) {
+            if (b.xf_cache) (void)hipFree(b.xf_cache);
+            b.xf_cache = nullptr;
+        }
+        if (what & tr_lbplan::kTable) {
+            if (b.d_xf_table) (void)hipFree(b.d_xf_table);
+            if (b.xf_table_ev) (void)hipEventDestroy(b.xf_table_ev);
+            b.d_xf_table = nullptr; b.xf_table_ev = nullptr; b.xf_table_stream = nullptr;
         }
     }
-    return (uint32_t)slots;
-}
-// the pool of a launch that reads no per-path cache (a static scene, or the frame's transform table instead: ADVICE round 5) is bounded by its own bytes alone
-static uint32_t wf_slot_count(const TrayDeviceScene* s) { return wf_slot_fit(s, wf_slot_wish(s, s->wf_req_slots), device_free_bytes(), s->wf_req_slots); }
-// The lanes of a moving scene's per-path transform cache (the largest pool a launch that reads it can have): the pool's rule, and the cache within two
-// fifths of the free memory + `reclaimable` (lb_fit). The library's rule and the environment alone: tray_scene_set_wavefront bounds the pool, not the cache.
-static uint32_t xf_cache_budget(const TrayDeviceScene* s, size_t reclaimable) {
-    const size_t free_b = device_free_bytes() + reclaimable;
-    uint64_t budget = free_b / 5 * 2;   // (two fifths of the free memory: the C5 stand-in has 2 .. 11 moving instances, 7 .. 39 GB at 32 M slots)
-    if (const char* e = getenv("TRAYHIP_XF_CACHE_BYTES")) budget = (uint64_t)std::max(0ll, atoll(e));
-    const uint64_t per_slot = (uint64_t)s->deferred_n_moving * TR_XF_REC * sizeof(float);
-    const uint64_t fit = budget / per_slot / TR_BLOCK * TR_BLOCK;
-    const uint64_t slots = std::min<uint64_t>(wf_slot_wish(s, 0u), std::max<uint64_t>(fit, (uint64_t)64 * TR_BLOCK));   // (at least 64 chunks: below that the schedule cannot fill the chip)
-    return wf_slot_fit(s, slots, free_b, 0u);
-}
-
-// frees the parts of the launch buffers `what` names (the caller has made sure that no launch still reads them)
-enum : unsigned { LB_POOL = 1u, LB_CACHE = 2u, LB_TABLE = 4u, LB_ALL = 7u };
-static void lb_drop(LaunchBuffers& b, unsigned what) {
-    if (what & LB_POOL) {
-        for (void* p : b.wf.allocs) (void)hipFree(p);
-        if (b.wf.h_done) (void)hipHostFree(b.wf.h_done);
-        b.wf = WfBuffers{};
+    int synchronise() { HIP_CHECK(hipDeviceSynchronize()); return TRAY_OK; }
+    int table_build(uint32_t stride) {
+        LaunchBuffers& b = s->lb;
+        const uint32_t n_index = tr_lbplan::kTimeIndices;   // (the build reads moving_ids, instances, spline tables, camera of `dev`: none of them is a launch buffer)
+        hipLaunchKernelGGL(k_xf_table_build, dim3(n_index / TR_BLOCK, stride), dim3(TR_BLOCK), 0, stream, s->dev, b.d_xf_table, stride, 0u, n_index);
+        HIP_CHECK(hipGetLastError());
+        // the build is ordered before this launch by the stream; the frame's later launches may come on other streams (tray_render_tiles_device /
+        // tray_render_shard_device take the caller's): they wait for this event instead of reading a table that is still being written
+        if (!b.xf_table_ev) HIP_CHECK(hipEventCreateWithFlags(&b.xf_table_ev, hipEventDisableTiming));
+        HIP_CHECK(hipEventRecord(b.xf_table_ev, stream));
+        b.xf_table_stream = stream;
+        return TRAY_OK;
     }
-    if (what & LB_CACHE) {   // (the lanes stay: before a wavefront cache is allocated anew they are its budget)
-        if (b.xf_cache) (void)hipFree(b.xf_cache);
-        b.xf_cache = nullptr; b.xf_cache_bytes = 0;
+    int table_wait() {
+        if (stream != s->lb.xf_table_stream && s->lb.xf_table_ev) HIP_CHECK(hipStreamWaitEvent(stream, s->lb.xf_table_ev, 0));
+        return TRAY_OK;
     }
-    if (what & LB_TABLE) {
-        if (b.d_xf_table) (void)hipFree(b.d_xf_table);
-        if (b.xf_table_ev) (void)hipEventDestroy(b.xf_table_ev);
-        b.d_xf_table = nullptr; b.xf_table_cap = b.xf_table_stride = 0u; b.xf_table_built = false; b.xf_table_ev = nullptr; b.xf_table_stream = nullptr;
+    int refusal() {
+        if (s->wavefront && !s->narrow_trees) { set_error("wavefront schedule: a BVH of more than 8 388 607 nodes or triangles (the traversal keeps a node as a 32-bit descriptor)"); return TRAY_E_UNSUPPORTED; }
+        if (s->wavefront && !s->ordered_boxes) { set_error("wavefront schedule: a BVH box with min > max (or NaN) on some axis; TRAYHIP_MODE=mega renders such a scene with the tile kernel"); return TRAY_E_UNSUPPORTED; }
+        return TRAY_OK;
     }
-}
+    void no_pool(uint32_t n_slots) {
+        set_error("the wavefront schedule's buffers could not be allocated even for " + std::to_string(n_slots) + " pool slots (" +
+                  std::to_string((n_slots * tr_lbplan::schedule_bytes_per_slot()) >> 20) + " MiB): " + tray_last_error());
+    }
+    void cache_short(uint32_t pool_slots, uint32_t lanes) {
+        set_error("wavefront schedule: " + std::to_string(pool_slots) + " pool slots but a per-path transform cache of " + std::to_string(lanes) + " paths");
+    }
+};
 
 extern "C" {
 
@@ -367,7 +412,8 @@ void tray_scene_destroy(TrayDeviceScene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     for (void* p : s->allocs) (void)hipFree(p);
-    lb_drop(s->lb, LB_ALL);
+    LbOps lb_ops{s};
+    tr_lbplan::drop(lb_ops, s->lb.st, tr_lbplan::kAll);
     if (s->d_smp) (void)hipFree(s->d_smp);
     if (s->nt.mem) (void)hipFree(s->nt.mem);
     if (s->nt.h_count) (void)hipHostFree(s->nt.h_count);
@@ -396,43 +442,6 @@ static const void* tile_kernel(const TrayDeviceScene* s) {
     const bool whitted = s->dev.integrator == TRAY_INTEGRATOR_WHITTED;
     if (s->animated) select_path_tiles<1>(s->feat, whitted, s->light_filter, take); else select_path_tiles<0>(s->feat, whitted, s->light_filter, take);
     return k;
-}
-
-// bytes of a per-path transform cache of `lanes` paths (records of the wavefront schedule / rows of columns of the tile kernel: dev_anim.h)
-static size_t xf_cache_bytes_for(const TrayDeviceScene* s, uint32_t lanes) {
-    return (size_t)s->deferred_n_moving * (s->wavefront ? TR_XF_REC : TR_XF_WORDS) * lanes * sizeof(float);
-}
-static int xf_cache_alloc(TrayDeviceScene* s, uint32_t lanes) {
-    const size_t bytes = xf_cache_bytes_for(s, lanes);
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hipMalloc of the per-path transform cache failed: " + std::to_string(bytes >> 20) + " MiB for " + std::to_string(s->deferred_n_moving) +
-                  " moving instances x " + std::to_string(lanes) + " paths (tray_scene_set_wavefront / TRAYHIP_WF_SLOTS / TRAYHIP_XF_CACHE_BYTES bound it)");
-        return TRAY_E_NOMEM;
-    }
-    s->lb.xf_cache = static_cast<float*>(p); s->lb.xf_cache_lanes = lanes; s->lb.xf_cache_bytes = bytes;
-    return TRAY_OK;
-}
-// Fits the launch buffers a frame update handed on (none for a new scene) to the frame of `s`: the cache keeps its lanes if it was made for this schedule
-// (the tile kernel's: for as many resident threads), else they are budgeted anew; the pool stays if it was made for these stacks and kernels and is no
-// larger than the cache's lanes or the wish (a pool that memory made smaller stays), or was sized for table launches and the table came along. A kept pool
-// serves as it is (launch_wavefront re-initialises chunk records and control words, the bins are zero between tiles). Returns whether the pool was kept.
-static bool lb_fit(TrayDeviceScene* s) {
-    LaunchBuffers& b = s->lb;
-    const bool moving = s->animated && s->deferred_n_moving > 0;
-    // (what the previous frame held counts as free, or the budget -- and with it the pool size -- would depend on which frame came first)
-    const size_t reclaimable = b.xf_cache_bytes + (b.wf.pool.data ? (size_t)F_COUNT * b.wf.pool.n_slots * sizeof(float) : 0);
-    const bool keep_lanes = moving && b.xf_cache_lanes != 0u && b.wavefront == s->wavefront && (s->wavefront || b.xf_cache_lanes == (uint32_t)s->n_blocks * TR_BLOCK);
-    const uint32_t lanes = !moving ? 0u : keep_lanes ? b.xf_cache_lanes : s->wavefront ? xf_cache_budget(s, reclaimable) : (uint32_t)s->n_blocks * TR_BLOCK;
-    if (!keep_lanes || b.xf_cache_bytes < xf_cache_bytes_for(s, lanes)) lb_drop(b, LB_CACHE);   // (every path fills its columns before it reads them)
-    b.xf_cache_lanes = lanes;
-    const bool keep_pool = b.wf.ready && s->wavefront && b.wf.stack_bytes == s->stack_bytes && b.wf.quad_stack_words == s->quad_stack_words &&
-                           b.wf.animated == s->animated && (b.wf.pool.n_slots <= (lanes ? lanes : wf_slot_wish(s, s->wf_req_slots)) || (b.last_used_table && b.d_xf_table));
-    if (!keep_pool) { lb_drop(b, LB_POOL); b.wf_shrunk = false; }
-    b.wavefront = s->wavefront;
-    b.xf_table_stride = 0u; b.xf_table_built = false; b.last_used_table = false;   // (the table is built anew by the frame's first launch that wants it)
-    return keep_pool;
 }
 
 // The trees of a scene in device order and what a frame update keeps of the donor's: host bookkeeping, nothing is uploaded here
@@ -657,24 +666,6 @@ static void scene_occupancy(TrayDeviceScene* s) {
     if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] tile kernel: %d workgroups per CU (dynamic LDS %u B)\n", per_cu, s->stack_bytes);
 }
 
-// The launch buffers: the previous frame's in one move (freeing and allocating the 20 GB of a table costs 4 s -- profiles/r06_d_frame_overheads.txt --, a
-// pool seconds more), then lb_fit drops what this frame cannot use
-static int scene_launch_buffers(TrayDeviceScene* s) {
-    TrayDeviceScene* donor = s->donor;
-    s->wf_req_slots = donor ? donor->wf_req_slots : 0u; s->wf_req_views = donor ? donor->wf_req_views : 0u; s->wf_req_slices = donor ? donor->wf_req_slices : 0u;
-    s->xf_table_req = donor ? donor->xf_table_req : -1;
-    if (donor) s->lb = std::exchange(donor->lb, LaunchBuffers{});
-    const uint32_t handed_slots = s->lb.wf.pool.n_slots, handed_table_use = s->lb.last_used_table;   // (TRAYHIP_STATS)
-    const bool pool_kept = lb_fit(s);
-    if (donor && getenv("TRAYHIP_STATS"))
-        fprintf(stderr, "[trayhip] frame update: pool %s (donor ready %d, wavefront %d, stack %u / %u B, quad stack %u / %u, animated %d / %d, donor slots %u, cache lanes %u, donor used the table %d, table buffer %s)\n",
-                pool_kept ? "kept" : "not kept", handed_slots ? 1 : 0, s->wavefront ? 1 : 0, donor->stack_bytes, s->stack_bytes, donor->quad_stack_words, s->quad_stack_words,
-                donor->animated ? 1 : 0, s->animated ? 1 : 0, handed_slots, s->lb.xf_cache_lanes, handed_table_use ? 1 : 0, s->lb.d_xf_table ? "kept" : "none");
-    // the tile kernel's cache is allocated here, the wavefront schedule's by the first launch that evaluates per path (launch_prepare)
-    if (s->dev.n_moving && !s->wavefront && !s->lb.xf_cache && xf_cache_alloc(s, s->lb.xf_cache_lanes) != TRAY_OK) return TRAY_E_NOMEM;
-    return TRAY_OK;
-}
-
 static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDeviceScene** out) {
     if (!f || !out) { set_error("tray_scene_create: null argument"); return TRAY_E_INVALID; }
     *out = nullptr;
@@ -695,7 +686,21 @@ static int scene_build(const TrayFlatScene* f, TrayDeviceScene* donor, TrayDevic
     if (rc != TRAY_OK) return rc;
     raise_lds_limit(s->stack_bytes);
     scene_occupancy(s);
-    if (scene_launch_buffers(s) != TRAY_OK) return TRAY_E_NOMEM;
+    {   // The launch buffers: the previous frame's in one move (freeing and allocating the 20 GB of a table costs 4 s -- profiles/r06_d_frame_overheads.txt --,
+        // a pool seconds more), then the plan drops what this frame cannot use and allocates the tile kernel's cache
+        s->wf_req_slots = donor ? donor->wf_req_slots : 0u; s->wf_req_views = donor ? donor->wf_req_views : 0u; s->wf_req_slices = donor ? donor->wf_req_slices : 0u;
+        s->xf_table_req = donor ? donor->xf_table_req : -1;
+        if (donor) s->lb = std::exchange(donor->lb, LaunchBuffers{});
+        const uint32_t handed_slots = s->lb.st.pool_slots, handed_table_use = s->lb.st.last_used_table;   // (TRAYHIP_STATS)
+        LbOps lb_ops{s};
+        bool pool_kept = false;
+        rc = tr_lbplan::frame(lb_ops, s->lb.st, lb_facts(s), &pool_kept);
+        if (donor && getenv("TRAYHIP_STATS"))
+            fprintf(stderr, "[trayhip] frame update: pool %s (donor ready %d, wavefront %d, stack %u / %u B, quad stack %u / %u, animated %d / %d, donor slots %u, cache lanes %u, donor used the table %d, table buffer %s)\n",
+                    pool_kept ? "kept" : "not kept", handed_slots ? 1 : 0, s->wavefront ? 1 : 0, donor->stack_bytes, s->stack_bytes, donor->quad_stack_words, s->quad_stack_words,
+                    donor->animated ? 1 : 0, s->animated ? 1 : 0, handed_slots, s->lb.st.cache_lanes, handed_table_use ? 1 : 0, s->lb.st.table ? "kept" : "none");
+        if (rc != TRAY_OK) return rc;
+    }
     s->donor = nullptr;
     *out = owner.release();
     return TRAY_OK;
@@ -725,12 +730,12 @@ int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* f) {
     const int before = g_device;
     g_device = s->device;
     const size_t owned_before = s->allocs.size();
-    const bool had_launch_buffers = s->lb.owns_any();
+    const bool had_launch_buffers = s->lb.st.owns_any();
     const int rc = scene_build(f, s, &n);
     g_device = before;
     if (rc != TRAY_OK) {   // if a buffer has moved to the half-built (and now destroyed) new state the handle can only be destroyed; a refusal before that leaves it as it was
         s->donor = nullptr;
-        if (s->allocs.size() != owned_before || (had_launch_buffers && !s->lb.owns_any())) s->broken = true;
+        if (s->allocs.size() != owned_before || (had_launch_buffers && !s->lb.st.owns_any())) s->broken = true;
         return rc;
     }
     n->sampler_kind = s->sampler_kind; n->smp_min = s->smp_min; n->smp_max = s->smp_max;   // (tray_scene_set_sampler belongs to the handle)
@@ -746,70 +751,6 @@ int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* f) {
 // smp_begin / smp_end: the sample range [smp_begin, smp_end) of the spp-sample LowDiscrepancy frame to render (tray_render_samples_device); 0 / 0 = all of [0, spp)
 static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
                         uint32_t spp, uint64_t seed, float* rgbw_dev, void* stream_, uint32_t smp_begin = 0u, uint32_t smp_end = 0u);
-
-// every buffer of the wavefront schedule for a pool of n_slots; on failure nothing stays allocated and TRAY_E_NOMEM is returned
-static int wf_alloc(TrayDeviceScene* s, uint32_t n_slots) {
-    WfBuffers& w = s->lb.wf;
-    auto grab = [&](size_t bytes, void** out) -> bool {
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("hipMalloc of " + std::to_string(bytes >> 20) + " MiB failed: " + hipGetErrorString(e));
-            lb_drop(s->lb, LB_POOL);
-            return false;
-        }
-        w.allocs.push_back(p);
-        *out = p;
-        return true;
-    };
-    void* p = nullptr;
-    w.n_chunks = n_slots / TR_BLOCK;
-    const uint32_t n_chunks = w.n_chunks;                    // (lb_drop resets the fields on a failed grab)
-    {   // the dynamic-fetch traversal's stacks and grid, then the shape of the queues and overflow columns they and the pool ask for (wavefront_plan.h)
-        int per_cu = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, s->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        // LDS stack entries per lane such that WF_TRACE_WAVES workgroups (4 waves each = one wave per SIMD) fit in the CU's 160 KB
-        // (a node on this kernel's stack is two words: descriptor and entry distance; up to three per expanded record)
-        const uint32_t full_depth = std::max(s->quad_stack_words, 8u);
-        uint32_t lds_depth = std::min<uint32_t>(full_depth, (160u * 1024u / WF_TRACE_WAVES) / (TR_BLOCK * (uint32_t)sizeof(uint32_t)));
-        if (const char* e = getenv("TRAYHIP_WF_LDS_DEPTH")) lds_depth = std::min<uint32_t>(full_depth, (uint32_t)std::max(1, atoi(e)));
-        w.trace_lds_depth = lds_depth;
-        w.trace_lds_bytes = lds_depth * TR_BLOCK * (uint32_t)sizeof(uint32_t);
-        hipError_t oe = s->animated ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 1>, TR_BLOCK, w.trace_lds_bytes)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wf_trace_dyn<0, 0>, TR_BLOCK, w.trace_lds_bytes);
-        if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-        w.n_blocks_trace = (uint32_t)(cus * per_cu);
-        w.lay = tr_wfplan::layout(n_chunks, full_depth, lds_depth, w.n_blocks_trace);
-        if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] dynamic-fetch traversal: %u of %u stack entries in LDS, %d workgroups per CU\n", lds_depth, full_depth, per_cu);
-    }
-    const tr_wfplan::Layout lay = w.lay;
-    if (!grab((size_t)F_COUNT * n_slots * sizeof(float), &p)) return TRAY_E_NOMEM;
-    w.pool.data = static_cast<float*>(p); w.pool.n_slots = n_slots; w.pool.seg_cap = wf_seg_cap(n_chunks);
-    if (!grab((size_t)n_chunks * sizeof(WfChunk), &p)) return TRAY_E_NOMEM;
-    w.d_chunks = static_cast<WfChunk*>(p);
-    if (!grab((size_t)n_chunks * ROWBIN_SIZE * sizeof(float), &p)) return TRAY_E_NOMEM;
-    w.d_bins = static_cast<float*>(p);
-    if (hipMemset(w.d_bins, 0, (size_t)n_chunks * ROWBIN_SIZE * sizeof(float)) != hipSuccess) { set_error("hipMemset of the row bins failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_DEVICE; }
-    if (!grab(2 * sizeof(uint32_t), &p)) return TRAY_E_NOMEM;
-    w.d_wf_counters = static_cast<uint32_t*>(p);
-    if (!grab((size_t)lay.queue_bytes, &p)) return TRAY_E_NOMEM;   // ray queues A, B, C, regeneration queue and the views' control words
-    w.d_queues = static_cast<uint32_t*>(p);
-    if (!grab((size_t)lay.bin_ctl_bytes, &p)) return TRAY_E_NOMEM;
-    w.d_bin_ctl = static_cast<uint32_t*>(p);
-    w.wf_sort = !(s->feat & FEAT_TEX);   // the kind-pure kernels read lobes from the material table; textured materials have theirs per hit
-    if (w.wf_sort) {   // shading queues of the material sort
-        if (!grab((size_t)lay.kind_bytes, &p)) return TRAY_E_NOMEM;
-        w.d_kind_queues = static_cast<uint32_t*>(p);
-    }
-    if (!grab((size_t)lay.ovf_bytes, &p)) return TRAY_E_NOMEM;
-    w.d_stack_overflow = static_cast<uint32_t*>(p);
-    if (hipHostMalloc(reinterpret_cast<void**>(&w.h_done), sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("hipHostMalloc failed"); lb_drop(s->lb, LB_POOL); return TRAY_E_NOMEM; }
-    w.stack_bytes = s->stack_bytes; w.quad_stack_words = s->quad_stack_words; w.animated = s->animated;
-    w.ready = true;
-    return TRAY_OK;
-}
 
 // Wavefront schedule: rounds of six stage kernels over the path pool until every tile is done. The views, a round's launches and the loop are
 // wavefront_plan.h's; what is this function's own: the streams and events of the views, their fork and join, the poll, the timing and the last_* fields.
@@ -1347,125 +1288,17 @@ static int launch_sampler(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_
     return TRAY_OK;
 }
 
-// The wavefront schedule's per-path cache, with a record for every pool slot: the budgeted lanes or the pool's slots. A pool larger than the budget (sized
-// for table launches) stays if a cache for all of it fits in two fifths of the free memory, else it goes and is sized anew for the cache; a cache too
-// small for the pool is allocated anew. Halved while hipMalloc refuses, never below the pool's slots or 64 chunks.
-static int xf_cache_ensure(TrayDeviceScene* s) {
-    LaunchBuffers& b = s->lb;
-    if (!s->wavefront || s->dev.n_moving == 0u) return TRAY_OK;
-    if (b.wf.ready && b.wf.pool.n_slots > b.xf_cache_lanes) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-        if (xf_cache_bytes_for(s, b.wf.pool.n_slots) > free_b / 5u * 2u) { HIP_CHECK(hipDeviceSynchronize()); lb_drop(b, LB_POOL); }
-    }
-    if (b.xf_cache && (!b.wf.ready || b.wf.pool.n_slots <= b.xf_cache_lanes)) return TRAY_OK;
-    if (b.xf_cache) { HIP_CHECK(hipDeviceSynchronize()); lb_drop(b, LB_CACHE); }
-    const uint32_t pool_slots = b.wf.ready ? b.wf.pool.n_slots : 0u, floor_lanes = b.wf.ready ? pool_slots : 64u * TR_BLOCK;
-    for (uint32_t lanes = std::max(b.xf_cache_lanes, pool_slots);; lanes = std::max(floor_lanes, lanes / 2u / TR_BLOCK * TR_BLOCK)) {
-        const int rc = xf_cache_alloc(s, lanes);
-        if (rc == TRAY_OK || lanes <= floor_lanes) return rc;
-    }
-}
-// The transform table of a moving scene's frame (dev_geom.h: xf_time_index; k_xf_table_build) with `stride` records per time index, built once per frame
-// on the launch stream by the first launch that reads it; TRAY_E_NOMEM if the buffer cannot be had
-static int xf_table_ensure(TrayDeviceScene* s, uint32_t stride, hipStream_t stream) {
-    LaunchBuffers& b = s->lb;
-    if (b.d_xf_table && b.xf_table_cap < stride) lb_drop(b, LB_TABLE);   // (the buffer handed on from the previous frame is too small for this frame's records)
-    if (b.d_xf_table && b.xf_table_stride != stride) { b.xf_table_stride = stride; b.xf_table_built = false; }
-    if (!b.d_xf_table) {
-        // room for what any frame of the sequence can move (instances whose transforms have several keyframes, tray_scene_create), if that much is to be had
-        uint32_t cap = std::max(stride, s->xf_movable);
-        void* p = nullptr;
-        // by the library's own rule (nobody asked for the table) it takes at most a third of what is free: on a device shared with other
-        // allocators 22.5 GB for eleven movers must not be what starves them
-        const bool own_rule = s->xf_table_req < 0 && !getenv("TRAYHIP_XF_TABLE");
-        for (;;) {   // (the sequence's headroom first, then this frame's records alone)
-            const size_t bytes = ((size_t)1 << 24) * cap * TR_XF_REC * sizeof(float);   // 2.1 GB per moving instance
-            bool room = true;
-            if (own_rule) {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) room = bytes <= free_b / 3u; else (void)hipGetLastError();
-            }
-            if (room && hipMalloc(&p, bytes) == hipSuccess) break;
-            (void)hipGetLastError(); p = nullptr;
-            if (cap == stride) return TRAY_E_NOMEM;
-            cap = stride;
-        }
-        b.d_xf_table = static_cast<float*>(p); b.xf_table_stride = stride; b.xf_table_cap = cap; b.xf_table_built = false;
-    }
-    if (!b.xf_table_built) {
-        const uint32_t n_index = 1u << 24;   // (the build reads moving_ids, instances, spline tables, camera of `dev`: none of them is a launch buffer)
-        hipLaunchKernelGGL(k_xf_table_build, dim3(n_index / TR_BLOCK, stride), dim3(TR_BLOCK), 0, stream, s->dev, b.d_xf_table, stride, 0u, n_index);
-        HIP_CHECK(hipGetLastError());
-        // the build is ordered before this launch by the stream; the frame's later launches may come on other streams (tray_render_tiles_device /
-        // tray_render_shard_device take the caller's): they wait for this event instead of reading a table that is still being written
-        if (!b.xf_table_ev) HIP_CHECK(hipEventCreateWithFlags(&b.xf_table_ev, hipEventDisableTiming));
-        HIP_CHECK(hipEventRecord(b.xf_table_ev, stream));
-        b.xf_table_stream = stream;
-        b.xf_table_built = true;
-    } else if (stream != b.xf_table_stream && b.xf_table_ev) {
-        HIP_CHECK(hipStreamWaitEvent(stream, b.xf_table_ev, 0));
-    }
-    return TRAY_OK;
-}
-
-// What a render call's kernels need of the launch buffers: 1. table or per-path evaluation -- the table when the launch needs every time index about twice
-// (from 3e7 camera samples on, a 1080p frame at 16 spp: the build costs what 1.7e7 evaluations cost, but takes 1.9 GB per moving instance), for every later
-// launch of the frame and the frames of a sequence that rendered through it, or as tray_scene_set_transform_table says; 2. the chosen one exists (else
-// the other serves); 3. the pool, kept or as large as the budget grants, halved while hipMalloc refuses (fragmentation, another scene's pool) down to
-// 64 chunks, then TRAY_E_NOMEM with the handle as it was; 4. s->launch_dev: `dev` with the cache, or the table in its place.
-#ifndef XF_TABLE_MIN_SAMPLES
-#define XF_TABLE_MIN_SAMPLES 30000000ull
-#endif
-static int launch_prepare(TrayDeviceScene* s, uint64_t samples, hipStream_t stream) {
-    LaunchBuffers& b = s->lb;
-    b.last_used_table = false;
-    const uint32_t stride = s->dev.n_moving + (s->camera_animated ? 1u : 0u);
-    bool table = false;
-    if (s->animated && stride != 0u) {
-        int want = s->xf_table_req;
-        if (const char* e = getenv("TRAYHIP_XF_TABLE")) want = atoi(e) != 0 ? 1 : 0;
-        if (want < 0) want = (samples >= XF_TABLE_MIN_SAMPLES || b.xf_table_built || b.d_xf_table) ? 1 : 0;
-        int rc = want ? TRAY_E_NOMEM : xf_cache_ensure(s);
-        if (rc == TRAY_E_NOMEM) {   // (the table wanted, or no room for the cache: the table is smaller from a few million slots on)
-            rc = xf_table_ensure(s, stride, stream);
-            table = rc == TRAY_OK;
-            if (rc == TRAY_E_NOMEM) rc = xf_cache_ensure(s);
-        }
-        if (rc != TRAY_OK) return rc;
-    }
-    b.last_used_table = table;
-    const bool reads_cache = s->wavefront && !table && s->dev.n_moving != 0u;   // (the tile kernel's cache has a column per resident thread: lb_fit)
-    if (s->wavefront && !s->narrow_trees) { set_error("wavefront schedule: a BVH of more than 8 388 607 nodes or triangles (the traversal keeps a node as a 32-bit descriptor)"); return TRAY_E_UNSUPPORTED; }
-    if (s->wavefront && !s->ordered_boxes) { set_error("wavefront schedule: a BVH box with min > max (or NaN) on some axis; TRAYHIP_MODE=mega renders such a scene with the tile kernel"); return TRAY_E_UNSUPPORTED; }
-    if (s->wavefront && !b.wf.ready) {
-        uint32_t n_slots = reads_cache ? std::min(b.xf_cache_lanes, wf_slot_wish(s, s->wf_req_slots)) : wf_slot_count(s);
-        for (;;) {
-            const int rc = wf_alloc(s, n_slots);
-            if (rc == TRAY_OK) break;
-            if (rc != TRAY_E_NOMEM) return rc;
-            if (n_slots / 2u < 64u * TR_BLOCK) {
-                set_error("the wavefront schedule's buffers could not be allocated even for " + std::to_string(n_slots) + " pool slots (" +
-                          std::to_string((n_slots * wf_bytes_per_slot()) >> 20) + " MiB): " + tray_last_error());
-                return TRAY_E_NOMEM;
-            }
-            n_slots = n_slots / 2u / TR_BLOCK * TR_BLOCK;
-            b.wf_shrunk = true;
-        }
-    }
-    // the stage kernels index the per-path cache by pool slot: it must have a record for every slot
-    if (reads_cache && (!b.xf_cache || b.wf.pool.n_slots > b.xf_cache_lanes)) {
-        set_error("wavefront schedule: " + std::to_string(b.wf.pool.n_slots) + " pool slots but a per-path transform cache of " + std::to_string(b.xf_cache ? b.xf_cache_lanes : 0u) + " paths");
-        return TRAY_E_DEVICE;
-    }
+// s->launch_dev, what the kernels of a render call get after launch_buffers_plan.h's prepare: `dev` with the cache, or the table in its place
+static void fill_launch_dev(TrayDeviceScene* s) {
+    const LaunchBuffers& b = s->lb;
+    const bool table = b.st.last_used_table;
     DevScene& d = s->launch_dev;
     d = s->dev;
-    d.xf_cache = b.xf_cache; d.xf_cache_lanes = b.xf_cache_lanes;
-    if (table) { d.xf_tab = b.d_xf_table; d.xf_tab_stride = b.xf_table_stride; }
+    d.xf_cache = b.xf_cache; d.xf_cache_lanes = b.st.cache_lanes;
+    if (table) { d.xf_tab = b.d_xf_table; d.xf_tab_stride = b.st.table_stride; }
     if (table && s->wavefront) {   // the stage kernels index the table by the path's time index; the tile kernel keeps its cache columns and fills them from it
-        d.xf_cache = b.d_xf_table; d.xf_table = 1u; d.xf_aos = 1u; d.xf_stride = b.xf_table_stride;
+        d.xf_cache = b.d_xf_table; d.xf_table = 1u; d.xf_aos = 1u; d.xf_stride = b.st.table_stride;
     }
-    return TRAY_OK;
 }
 
 static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_count, uint32_t chunk, uint32_t chunk_stride,
@@ -1491,20 +1324,22 @@ static int launch_tiles(TrayDeviceScene* s, const uint2* tiles, uint32_t tile_co
     const uint32_t n_smp = tr_rules::range_samples(spp, smp_begin, smp_end);
     if (s->sampler_kind != TRAY_SAMPLER_LOW_DISCREPANCY || s->deforming) return launch_sampler(s, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
     s->last_was_wavefront = false;
-    const bool had_pool = s->lb.wf.ready;
+    const bool had_pool = s->lb.st.pool;
     {
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = launch_prepare(s, (uint64_t)tile_count * 64u * n_smp, stream);
+        LbOps lb_ops{s, stream};
+        const int rc = tr_lbplan::prepare(lb_ops, s->lb.st, lb_facts(s), (uint64_t)tile_count * 64u * n_smp);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] launch buffers prepared in %.1f ms (table %s, %u of %u records per index in use; pool %s: %u slots)\n",
-                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), s->lb.last_used_table ? "on" : "off",
-                                             s->lb.xf_table_stride, s->lb.xf_table_cap, had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
+                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), s->lb.st.last_used_table ? "on" : "off",
+                                             s->lb.st.table_stride, s->lb.st.table_cap, had_pool ? "kept" : "allocated", s->lb.st.pool_slots);
         if (rc != TRAY_OK) return rc;
+        fill_launch_dev(s);
     }
     if (s->wavefront) {
         const auto t0 = std::chrono::steady_clock::now();
         const int rc = launch_wavefront(s, tiles, tile_count, chunk, chunk_stride, spp, kf, rgbw_dev, stream, smp_begin, smp_end);
         if (getenv("TRAYHIP_STATS")) fprintf(stderr, "[trayhip] wavefront launch enqueued in %.1f ms (pool %s: %u slots)\n",
-                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->lb.wf.pool.n_slots);
+                                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), had_pool ? "kept" : "allocated", s->lb.st.pool_slots);
         return rc;
     }
     const uint32_t levels = tr_rules::tile_levels(tile_count, (uint32_t)s->n_blocks, n_smp);   // items per tile: progressive slices
@@ -1786,13 +1621,13 @@ int tray_multi_set_transform_table(TrayMultiScene* m, int mode) {
 int tray_debug_transform_table(TrayDeviceScene* s, uint32_t n, uint32_t* n_differ) {
     if (!s || !n_differ) { set_error("tray_debug_transform_table: null argument"); return TRAY_E_INVALID; }
     *n_differ = 0;
-    if (!s->lb.d_xf_table || !s->lb.xf_table_built) { set_error("tray_debug_transform_table: this frame has no transform table (no launch wanted one yet)"); return TRAY_E_INVALID; }
+    if (!s->lb.st.table || !s->lb.st.table_built) { set_error("tray_debug_transform_table: this frame has no transform table (no launch wanted one yet)"); return TRAY_E_INVALID; }
     HIP_CHECK(hipSetDevice(s->device));
     uint32_t* d_bad = nullptr;
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_bad), sizeof(uint32_t)));
     hipError_t e = hipMemset(d_bad, 0, sizeof(uint32_t));
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_xf_table_check, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, nullptr, s->dev, s->lb.d_xf_table, s->lb.xf_table_stride, n, d_bad);
+        hipLaunchKernelGGL(k_xf_table_check, dim3((n + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, nullptr, s->dev, s->lb.d_xf_table, s->lb.st.table_stride, n, d_bad);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(n_differ, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost);
@@ -1805,13 +1640,13 @@ int tray_scene_set_wavefront(TrayDeviceScene* s, uint32_t pool_slots, uint32_t v
     if (s->broken) { set_error("tray_scene_set_wavefront: the handle is only good for tray_scene_destroy after a failed frame update"); return TRAY_E_INVALID; }
     if (views > (uint32_t)WF_PIPES_MAX) { set_error("tray_scene_set_wavefront: at most " + std::to_string(WF_PIPES_MAX) + " views"); return TRAY_E_INVALID; }
     if (slices > WF_MAX_SLICES || (slices & (slices - 1u)) != 0u) { set_error("tray_scene_set_wavefront: slices per tile must be 0 or a power of two up to " + std::to_string(WF_MAX_SLICES)); return TRAY_E_INVALID; }
-    const uint32_t before = wf_slot_wish(s, s->wf_req_slots);
+    const bool pool_goes = tr_lbplan::wish_changed(s->lb.st, s->n_tiles, s->wf_req_slots, pool_slots);
     s->wf_req_slots = pool_slots; s->wf_req_views = views; s->wf_req_slices = slices;
-    if (s->lb.wf.ready && wf_slot_wish(s, s->wf_req_slots) != before) {   // another pool size: the buffers go, the next render call allocates them anew
+    if (pool_goes) {   // another pool size: the buffers go, the next render call allocates them anew
         HIP_CHECK(hipSetDevice(s->device));
         HIP_CHECK(hipDeviceSynchronize());
-        lb_drop(s->lb, LB_POOL);
-        s->lb.wf_shrunk = false;
+        LbOps ops{s};
+        tr_lbplan::drop_pool(ops, s->lb.st);
     }
     return TRAY_OK;
 }
@@ -1828,16 +1663,17 @@ int tray_last_schedule(TrayDeviceScene* s, TrayScheduleInfo* out) {
     std::memset(out, 0, sizeof *out);
     out->wavefront = s->wavefront ? 1u : 0u;
     out->launched_wavefront = s->last_was_wavefront ? 1u : 0u;
-    out->pool_slots = s->lb.wf.pool.n_slots; out->chunks = s->lb.wf.n_chunks;
+    const tr_lbplan::State& st = s->lb.st;   // (a part that does not exist has no slots, bytes or records)
+    out->pool_slots = st.pool_slots; out->chunks = s->lb.wf.n_chunks;
     out->views = s->last_was_wavefront ? s->last_views : 0u; out->slices = s->last_was_wavefront ? s->last_slices : 0u;
-    out->pool_bytes = s->lb.wf.pool.data ? (uint64_t)F_COUNT * s->lb.wf.pool.n_slots * sizeof(float) : 0u;
-    out->schedule_bytes = s->lb.wf.pool.data ? (uint64_t)s->lb.wf.pool.n_slots * wf_bytes_per_slot() : 0u;
-    out->xf_cache_bytes = s->lb.xf_cache_bytes;
+    out->pool_bytes = tr_lbplan::pool_bytes(st.pool_slots);
+    out->schedule_bytes = st.pool_slots * tr_lbplan::schedule_bytes_per_slot();
+    out->xf_cache_bytes = st.cache_bytes;
     out->n_moving = s->dev.n_moving;
     out->tile_workgroups = (uint32_t)s->n_blocks;
-    out->transform_table = s->lb.last_used_table ? 1u : 0u;
+    out->transform_table = st.last_used_table ? 1u : 0u;
     out->binned_stages = (s->last_was_wavefront && WF_FOLD_C) ? s->wf_bin_stages : 0u;
-    out->xf_table_bytes = s->lb.d_xf_table ? ((uint64_t)1 << 24) * s->lb.xf_table_cap * TR_XF_REC * sizeof(float) : 0u;   // (the buffer: sized for what any frame of the sequence can move)
+    out->xf_table_bytes = tr_lbplan::table_bytes(st.table_cap);   // (the buffer: sized for what any frame of the sequence can move)
     return TRAY_OK;
 }
 

@@ -85,7 +85,7 @@ inline void plan_motion(const TrayFlatScene* f, ScenePlan& p) {
     p.moving_ids.assign(p.n_moving, 0u);
     for (uint32_t i = 0; i < f->n_instances; ++i)
         if (f->instances[i].animated && f->instances[i].moving_slot < p.n_moving) p.moving_ids[f->instances[i].moving_slot] = i;
-    // how many records per time index a later frame of this scene can need (xf_table_ensure sizes the table's buffer once)
+    // how many records per time index a later frame of this scene can need (launch_buffers_plan.h: table_ensure sizes the table's buffer once)
     auto movable = [&](uint32_t first, uint32_t count) {
         for (uint32_t l = first; l < first + count && l < f->n_xf_levels; ++l) if (f->xf_levels[l].kf_count > 1u) return true;
         return false;

@@ -391,9 +391,9 @@ int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32
  *   synchronises on `stream` once per round (it reads the number of active tiles) and returns when it is done.
  * - Border pixels. The reconstruction filter reaches across tile borders. With a filter that has negative lobes (Mitchell-Netravali), a
  *   pixel next to tiles that ended with many times its tile's samples can get a total weight w near zero or below it, so that rgb / w
- *   resolves to black or to a saturated value; a uniform render has no such pixel. Callers should treat pixels with w <= 0, or with rgb / w
- *   far outside the image's range, as missing ("Rendering to a noise threshold": measured counts and the planned fix, a bound on
- *   the ratio of n_t between neighbouring tiles).
+ *   resolves to black or to a saturated value; a uniform render has no such pixel. tray_scene_set_noise_ratio (below) bounds the ratio of n_t
+ *   between neighbouring tiles, which keeps every pixel's own samples dominant; it is off by default, and without it callers should treat
+ *   pixels with w <= 0, or with rgb / w far outside the image's range, as missing ("Rendering to a noise threshold": measured counts).
  * - Determinism. The films are sums of float atomics, so a tile whose error lies within rounding of `threshold` may be decided either way
  *   from one run to the next. What the call returns is always the film of exactly the reported [0, n_t) of every tile.
  * Returns TRAY_E_INVALID unless 2 <= min_spp <= max_spp are powers of two, threshold >= 0 (not NaN), no pointer is null and the two films are
@@ -401,6 +401,28 @@ int tray_render_first_hit_device(TrayDeviceScene* s, uint32_t tile_start, uint32
 int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t min_spp, uint32_t max_spp,
                                     float threshold, uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples,
                                     float* tile_error, void* stream);
+
+/* Neighbour bound of the two noise-target calls (tray_render_noise_target_device, tray_render_noise_target_filtered_device): with max_ratio R,
+ * 0 (off, the default) or a power of two in [2, 65536], neighbouring tiles end with sample counts at most R apart, max(n) <= R min(n).
+ * - Neighbours. A tile's neighbours are the up to eight tiles around it in the grid of 8 x 8 tiles that belong to the call's range
+ *   [tile_start, tile_start + tile_count). Tiles outside the range never render and do not count.
+ * - Per-tile state. Every tile carries its own n_t: min_spp after round 0. Whenever a tile renders a round it renders its own next doubling
+ *   [n_t, 2 n_t), split at 1.5 n_t into even and odd as above; tiles of different n_t may render in the same round.
+ * - After a round's errors are taken, the set that renders the next round is the least set S such that
+ *   (a) S holds every tile the stopping rule keeps: !(error < threshold) and n_t < max_spp; and
+ *   (b) S holds every tile t with n_t < max_spp that has a neighbour u with n_u' > R n_t, where n_u' = 2 n_u if u is in S and n_u otherwise.
+ *   (b) is a fixed point -- a pulled tile can pull its own neighbours --; the least one is unique, so S does not depend on an order of evaluation.
+ * - A pulled tile's error is measured after its round like any tile's, and the stopping rule applies to it: tile_error stays the error of the
+ *   last round the tile rendered. Within a round the tiles render and are measured by n_t, the smallest first, each group's error from the
+ *   films as they stand when it is taken. The rounds end when S is empty.
+ * - At the end the films are exactly the film of [0, n_t) of every tile, and max(n) <= R min(n) for every pair of neighbouring tiles.
+ * - Cost. A bounded round reads one count per value of n_t (still one synchronisation per round) and launches one pair of renders and one
+ *   error step per value of n_t that has tiles, log2(max_spp / min_spp) pull steps and up to as many list compactions. max_spp is at most
+ *   32768 min_spp under a bound (16 values of n_t; TRAY_E_INVALID from the render call otherwise, before any device call).
+ * - R = 0 is the call without the bound: the same launches in the same order, the same bits.
+ * The setting belongs to the handle, as tray_scene_set_sampler's: it stays across tray_scene_update_frame and is read by both calls. Returns
+ * TRAY_E_INVALID for a null scene or any other value. */
+int tray_scene_set_noise_ratio(TrayDeviceScene* s, uint32_t max_ratio);
 
 /* Denoise a frame rendered as two half films (tray_render_noise_target_device's even / odd, or two sample ranges of equal size from
  * tray_render_samples_device): dual-buffer non-local means (Rousselle, Knaus, Zwicker 2012). The difference of the halves estimates the noise

@@ -312,10 +312,20 @@ class Hip:
                     self.last_timing = t
                 yield end, rt
 
-    def _noise_target_device(self, dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out):
+    def _noise_target_device(self, dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out, max_ratio=None):
         """one noise-target call on the current stream into the zeroed (h, w, 4) tensors even / odd: error="raw" is
-        tray_render_noise_target_device, "filtered" tray_render_noise_target_filtered_device (with its denoised output if want_out). Returns
-        (tile_samples, tile_error, out tensor or None)."""
+        tray_render_noise_target_device, "filtered" tray_render_noise_target_filtered_device (with its denoised output if want_out). max_ratio:
+        tray_scene_set_noise_ratio for this call alone (the device scene is back at 0 afterwards). Returns (tile_samples, tile_error, out tensor
+        or None)."""
+        if max_ratio is None:
+            return self._noise_target_call(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out)
+        check(lib().tray_scene_set_noise_ratio(dev, int(max_ratio)))
+        try:
+            return self._noise_target_call(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out)
+        finally:
+            lib().tray_scene_set_noise_ratio(dev, 0)   # (a device scene other methods reuse keeps their behaviour)
+
+    def _noise_target_call(self, dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out):
         import torch
         samples, err = np.zeros(n, np.uint32), np.zeros(n, np.float32)
         sp, ep = samples.ctypes.data_as(C.POINTER(C.c_uint32)), err.ctypes.data_as(C.POINTER(C.c_float))
@@ -337,13 +347,15 @@ class Hip:
         return samples, err, out
 
     def render_noise_target(self, scene, rt, config, threshold, min_spp=16, error="raw", radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
-                            k=_lib.TRAY_DENOISE_K):
+                            k=_lib.TRAY_DENOISE_K, max_ratio=None):
         """config.select_blocks of the frame rendered to a noise threshold (tray_render_noise_target_device): every tile takes the
         power-of-two prefix [0, n_t) of the round_spp(config.spp)-sample LowDiscrepancy frame, min_spp <= n_t <= that spp, at which its
         two-buffer error drops below `threshold`. error="filtered" takes that error from the two cross-filtered halves of the films instead
         (tray_render_noise_target_filtered_device with radius, patch, k): the rule for a frame that will be denoised. The image (even + odd film,
-        unfiltered either way) is added into rt. Returns (tile_samples, tile_error): numpy arrays of n_t and the last error per tile, in BlockQueue
-        order. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        unfiltered either way) is added into rt. max_ratio (a power of two >= 2) bounds the ratio of n_t between neighbouring tiles
+        (tray_scene_set_noise_ratio, for this call alone), so that no border pixel's weight is cancelled by a neighbour's negative filter lobes.
+        Returns (tile_samples, tile_error): numpy arrays of n_t and the last error per tile, in BlockQueue order. LowDiscrepancy only (TrayError
+        TRAY_E_UNSUPPORTED otherwise)."""
         import torch
         if error not in ("raw", "filtered"):
             raise ValueError(f"error must be 'raw' or 'filtered', not {error!r}")
@@ -355,7 +367,7 @@ class Hip:
         with torch.cuda.device(self.device):
             even = torch.zeros((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
             odd = torch.zeros_like(even)
-            samples, err, _ = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, False)
+            samples, err, _ = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, False, max_ratio)
             rt.add_pixels((even + odd).reshape(-1).cpu().numpy())
         t = _lib.TrayKernelTiming()
         if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
@@ -498,7 +510,7 @@ class Hip:
 
     def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
                         k=_lib.TRAY_DENOISE_K, error="raw", passes=1, radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2,
-                        k2=_lib.TRAY_DENOISE_K2, demodulate=False, feature_spp=None):
+                        k2=_lib.TRAY_DENOISE_K2, demodulate=False, feature_spp=None, max_ratio=None):
         """config.select_blocks of the frame rendered as two half films and denoised on the device (tray_denoise_device); the RGBW output (weight 1)
         is added into rt. With `threshold` the films are the even / odd film of a noise-target render (see render_noise_target; error="filtered"
         stops on the error of the denoised image and takes the output from that same call) and (tile_samples, tile_error) is returned; without it
@@ -506,10 +518,13 @@ class Hip:
         passes=2 filters the films as denoise(passes=2) does; the stopping rule of error="filtered" measures one pass's image, so the two do not
         combine. demodulate=True divides the colour by the frame's first-hit albedo before the filter and multiplies it back in afterwards
         (denoise(albedo=...)): the albedo film is rendered from the samples [0, feature_spp or spp) of the same frame and seed; it does not
-        combine with error="filtered" either. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
+        combine with error="filtered" either. max_ratio bounds the ratio of n_t between neighbouring tiles of the noise-target render (see
+        render_noise_target) and needs a threshold. LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
         import torch
         if error not in ("raw", "filtered"):
             raise ValueError(f"error must be 'raw' or 'filtered', not {error!r}")
+        if max_ratio is not None and threshold is None:
+            raise ValueError("render_denoised: max_ratio bounds a noise-target render and needs a threshold")
         second = self._second_pass("render_denoised", passes, radius2, patch2, k2)
         if second is not None and error == "filtered":
             raise ValueError("render_denoised: error='filtered' stops on one pass's image and takes it from that call; use passes=1 with it")
@@ -536,7 +551,7 @@ class Hip:
                     self.render_samples_device(scene, config.current_frame, (start, count), spp, rng, film.data_ptr(), stream or None)
             else:
                 n = len(BlockQueue((w, h), (8, 8), (start, count)).blocks)
-                samples, err, out = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, True)
+                samples, err, out = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, True, max_ratio)
                 result = (samples, err)
             t = _lib.TrayKernelTiming()
             if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:   # (the last render call's: the whole noise-target call, or the second range)

@@ -172,6 +172,7 @@ SYMBOLS = {
     "tray_scene_update_frame": (C.c_int, [C.c_void_p, _P(TrayFlatScene)]),
     "tray_scene_destroy": (None, [C.c_void_p]),
     "tray_scene_set_sampler": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "tray_scene_set_noise_ratio": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tray_multi_set_sampler": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "tray_scene_set_wavefront": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "tray_multi_set_wavefront": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),

@@ -11,6 +11,7 @@
 #include "kernel_ranges.h"
 #include "kernel_tiles.h"
 #include "noise.h"
+#include "nbound.h"
 #include "denoise.h"
 #include "guide.h"
 #include "temporal.h"
@@ -85,9 +86,14 @@ struct LaunchBuffers {
 // list (coordinates and queue indices; the error kernel reads it before the compaction rewrites it, in stream order, so one list serves every round), the
 // next-round flags, the samples taken and the errors (by queue index), and the list's length; h_count is the pinned pair of words the host reads the
 // round's counts through (the tile list's length; behind it, for the filtered rule, the block list's)
+// bound: the neighbour bound's own buffers (tray_scene_set_noise_ratio; noise_plan.h's bound_layout), allocated by the first bounded call and anew when a
+// call needs more; h_counts: the pinned words a bounded round's counts are read through (one per level list, and the block count)
 struct NoiseBuffers {
     void* mem = nullptr;
     uint32_t* h_count = nullptr;
+    void* bound = nullptr;
+    uint64_t bound_bytes = 0;
+    uint32_t* h_counts = nullptr;
 };
 struct TrayDeviceScene {
     int device = 0;
@@ -144,6 +150,7 @@ struct TrayDeviceScene {
     void* d_smp = nullptr;            // [state u32 | running average f32 | luminances f32 x cap] per pixel of a batch of tiles
     size_t smp_bytes = 0;
     NoiseBuffers nt;                  // tray_render_noise_target_device (allocated on first use, kept across frame updates)
+    uint32_t noise_ratio = 0;         // tray_scene_set_noise_ratio: 0 = no bound on the ratio of n_t between neighbouring tiles
     bool accumulate = false;          // a tray_render_noise_target_device call is running: its launches add to one set of stats, between its own events
 };
 
@@ -417,6 +424,8 @@ void tray_scene_destroy(TrayDeviceScene* s) {
     if (s->d_smp) (void)hipFree(s->d_smp);
     if (s->nt.mem) (void)hipFree(s->nt.mem);
     if (s->nt.h_count) (void)hipHostFree(s->nt.h_count);
+    if (s->nt.bound) (void)hipFree(s->nt.bound);
+    if (s->nt.h_counts) (void)hipHostFree(s->nt.h_counts);
     for (int k = 0; k < WF_PIPES_MAX; ++k) {
         if (s->wf_streams[k]) (void)hipStreamDestroy(s->wf_streams[k]);
         if (s->wf_join[k]) (void)hipEventDestroy(s->wf_join[k]);
@@ -739,6 +748,7 @@ int tray_scene_update_frame(TrayDeviceScene* s, const TrayFlatScene* f) {
         return rc;
     }
     n->sampler_kind = s->sampler_kind; n->smp_min = s->smp_min; n->smp_max = s->smp_max;   // (tray_scene_set_sampler belongs to the handle)
+    n->noise_ratio = s->noise_ratio;   // (and so does tray_scene_set_noise_ratio)
     std::swap(n->d_smp, s->d_smp); std::swap(n->smp_bytes, s->smp_bytes);
     std::swap(n->nt, s->nt);
     std::swap(*s, *n);        // the handle keeps its identity; n now owns what the new frame did not take over
@@ -834,6 +844,15 @@ int tray_scene_set_sampler(TrayDeviceScene* s, uint32_t kind, uint32_t min_spp, 
     return TRAY_OK;
 }
 
+int tray_scene_set_noise_ratio(TrayDeviceScene* s, uint32_t max_ratio) {
+    if (!s) { set_error("tray_scene_set_noise_ratio: null argument"); return TRAY_E_INVALID; }
+    if (max_ratio != 0u && (max_ratio < 2u || max_ratio > (1u << 16) || (max_ratio & (max_ratio - 1u)) != 0u)) {
+        set_error("tray_scene_set_noise_ratio: max_ratio must be 0 or a power of two in [2, 65536]"); return TRAY_E_INVALID;
+    }
+    s->noise_ratio = max_ratio;
+    return TRAY_OK;
+}
+
 int tray_render_tiles_device(TrayDeviceScene* s, uint32_t tile_start, uint32_t tile_count, uint32_t spp, uint64_t seed,
                              float* rgbw_dev, void* stream_) {
     if (!s || !rgbw_dev) { set_error("tray_render_tiles_device: null argument"); return TRAY_E_INVALID; }
@@ -926,12 +945,26 @@ struct NoiseOps {   // the launch groups of the plan's schedule
     void compact(const void* queue, const uint32_t* active, uint32_t n, void* list, uint32_t* list_q, uint32_t* count) {
         tr_noise::compact(stream, xy(queue), active, n, static_cast<uint2*>(list), list_q, count);
     }
-    int read(const uint32_t* counts, uint32_t n_words, uint32_t* host) {   // through the scene's pinned words
+    int read(const uint32_t* counts, uint32_t n_words, uint32_t* host) {   // through the scene's pinned words (a bounded call's: those of its own)
+        uint32_t* const pinned = s->nt.h_counts ? s->nt.h_counts : s->nt.h_count;
+        if (n_words > (s->nt.h_counts ? nt::kMaxLevels + 1u : 2u)) { set_error("a noise-target round reads more count words than the scene has pinned"); return TRAY_E_DEVICE; }
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(s->nt.h_count, counts, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(pinned, counts, n_words * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
-        std::copy(s->nt.h_count, s->nt.h_count + n_words, host);
+        std::copy(pinned, pinned + n_words, host);
         return TRAY_OK;
+    }
+    // the neighbour bound's groups (libtrayhip_nbound.so)
+    int grid(const void* queue, uint32_t n, uint32_t* map) {
+        HIP_CHECK(tr_nbound::grid(stream, xy(queue), n, nt::grid_w(width), nt::grid_h(height), map));
+        return TRAY_OK;
+    }
+    void pull(const void* queue, uint32_t n, const uint32_t* map, const uint32_t* samples, uint32_t* active, uint32_t max_ratio, uint32_t max_spp_) {
+        tr_nbound::pull(stream, xy(queue), n, map, nt::grid_w(width), nt::grid_h(height), samples, active, max_ratio, max_spp_);
+    }
+    void compact_level(const void* queue, const uint32_t* active, const uint32_t* samples, uint32_t n_level, uint32_t n, void* list, uint32_t* list_q,
+                       uint32_t* count) {
+        tr_nbound::compact_level(stream, xy(queue), active, samples, n_level, n, static_cast<uint2*>(list), list_q, count);
     }
     int final_filter(const float* even, const float* odd, uint32_t radius, uint32_t patch, float k, float* out, void* records) {
         tr_denoise::denoise(stream, even, odd, width, height, radius, patch, k, out, records);
@@ -958,13 +991,24 @@ static int noise_target_call(TrayDeviceScene* s, uint32_t tile_start, uint32_t t
     const nt::TileLayout tl = nt::tile_layout(s->n_tiles);
     if (!b.mem) HIP_CHECK(hipMalloc(&b.mem, (size_t)tl.total));
     if (!b.h_count) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.h_count), 2u * sizeof(uint32_t), hipHostMallocDefault));
+    // the neighbour bound (over two levels or more: one level has nothing to bound): its buffers on first use, anew if this call's levels need more
+    nt::Bound bound{s->noise_ratio, nt::grid_w(s->dev.width), nt::grid_h(s->dev.height), nullptr};
+    const bool bounded = s->noise_ratio != 0u && min_spp < max_spp;
+    if (bounded) {
+        const uint64_t need = nt::bound_layout(s->n_tiles, bound.grid_w, bound.grid_h, nt::levels_of(min_spp, max_spp)).total;
+        if (b.bound && b.bound_bytes < need) { HIP_CHECK(hipStreamSynchronize(stream)); HIP_CHECK(hipFree(b.bound)); b.bound = nullptr; b.bound_bytes = 0; }
+        if (!b.bound) { HIP_CHECK(hipMalloc(&b.bound, (size_t)need)); b.bound_bytes = need; }
+        if (!b.h_counts) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&b.h_counts), (nt::kMaxLevels + 1u) * sizeof(uint32_t), hipHostMallocDefault));
+        bound.mem = b.bound;
+    }
     HIP_CHECK(hipMemsetAsync(s->d_stats, 0, WF_STAT_SLOTS * sizeof(DevStats), stream));   // (the launches below add to them: s->accumulate)
     HIP_CHECK(hipMemsetAsync(s->d_retraced, 0, sizeof(uint32_t), stream));
     HIP_CHECK(hipEventRecord(s->ev0, stream));
     uint32_t launches = 0u;
     NoiseOps ops{s, stream, seed, max_spp, s->dev.width, s->dev.height};
     s->accumulate = true;
-    const nt::Refusal no = nt::run(ops, nt::Target{s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, even_dev, odd_dev, b.mem, s->n_tiles}, f, &launches);
+    const nt::Refusal no = nt::run(ops, nt::Target{s->d_tiles + tile_start, tile_count, min_spp, max_spp, threshold, even_dev, odd_dev, b.mem, s->n_tiles}, f, &launches,
+                                   bounded ? &bound : nullptr);
     s->accumulate = false;
     if (no.rc != TRAY_OK) {   // (a failed call has set the error itself; the renders before it have set timing_valid)
         if (!no.msg.empty()) set_error(no.msg);
@@ -984,6 +1028,7 @@ int tray_render_noise_target_device(TrayDeviceScene* s, uint32_t tile_start, uin
                                     uint64_t seed, float* even_dev, float* odd_dev, uint32_t* tile_samples, float* tile_error, void* stream_) {
     const nt::Refusal no = nt::target_rules("tray_render_noise_target_device", noise_scene(s), min_spp, max_spp, threshold, even_dev, odd_dev, tile_samples, tile_error);
     if (no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
+    if (const nt::Refusal nb = nt::bound_rules("tray_render_noise_target_device", s->noise_ratio, min_spp, max_spp); nb.rc != TRAY_OK) { set_error(nb.msg); return nb.rc; }
     return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, nullptr, tile_samples, tile_error, stream_);
 }
 
@@ -995,6 +1040,7 @@ int tray_render_noise_target_filtered_device(TrayDeviceScene* s, uint32_t tile_s
     const nt::Refusal no = nt::filtered_rules("tray_render_noise_target_filtered_device", noise_scene(s), min_spp, max_spp, threshold, even_dev, odd_dev, radius,
                                               patch, k, out_dev, scratch_dev, tile_samples, tile_error);
     if (no.rc != TRAY_OK) { set_error(no.msg); return no.rc; }
+    if (const nt::Refusal nb = nt::bound_rules("tray_render_noise_target_filtered_device", s->noise_ratio, min_spp, max_spp); nb.rc != TRAY_OK) { set_error(nb.msg); return nb.rc; }
     const nt::Filter f{radius, patch, k, scratch_dev, out_dev};
     return noise_target_call(s, tile_start, tile_count, min_spp, max_spp, threshold, seed, even_dev, odd_dev, &f, tile_samples, tile_error, stream_);
 }

@@ -27,6 +27,17 @@
 #ifndef TR_LEAN_PICK
 #define TR_LEAN_MIS_PDF_FIRST
 #endif
+// A second class of item, which TR_LEAN_TILES does NOT turn on by itself (kernel_fold.hip, libtrayhip_foldmis.so, defines it next to TR_LEAN_TILES) -- re-timed: keeps
+// every sample's radiance and the counts, moves the step a sample finishes in, and with it the order of the film's f32 sums:
+//   TR_LEAN_FOLD_MIS_RAY   k_path_tiles' step loop: when fewer than TR_LEAN_FOLD_MIN_LANES lanes of the wave have a stage C ray, the wave skips
+//                          the third traversal pass; those lanes (LF_FOLD) trace the ray in the next step's stage A pass -- the same kind of ray:
+//                          closest hit, from bsdf.p, 0.001 .. inf --, close the vertex there and sit out that step's stage B
+//                          (the instantiations of PDF_FIRST: after it LF_MIS survives for about one lane in a hundred on cornell_box)
+#endif
+#ifdef TR_LEAN_FOLD_MIS_RAY
+#ifndef TR_LEAN_FOLD_MIN_LANES   // stage C runs as a pass of its own from this many rays on (65: never, every ray is folded); profiles/r24_lean_fold_mis_ray.txt
+#define TR_LEAN_FOLD_MIN_LANES 8
+#endif
 #endif
 
 namespace tr {
@@ -89,6 +100,10 @@ enum : uint32_t {
     LF_SHADOW = 4u,      // stage B has an occlusion ray to trace
     LF_MIS = 8u,         // stage C has a BSDF-sampled light ray to trace
     LF_LAST = 16u,       // the path ends at this vertex (decided in stage B, applied in stage C)
+#ifdef TR_LEAN_FOLD_MIS_RAY
+    LF_FOLD = 16384u,    // the vertex is still open: its stage C ray is traced in the next step's stage A pass (k_path_tiles; clear of wavefront.h's WF_ bits)
+    LF_SIT = 32768u,     // the lane closed a folded vertex in this step's stage A and sits out the rest of the step: its next ray is ready
+#endif
     LF_MIS_MISS = 1024u,     // the BSDF-sampled light ray cannot hit the light's own primitive: it counts as a ray, it is not traced
     LF_MIS_UNTESTED = 2048u  // LF_MIS set for a specular sample: no Light::pdf looked at the light's primitive (mis_ray_filter)
 };

@@ -5,6 +5,10 @@
 // TR_LEAN_TILES is where tile-kernel performance work goes: every edit to kernels.hip and the dev_*.h headers sits inside a sub-macro that
 // TR_LEAN_TILES turns on (dev_integrator.h lists them), with the existing text as the #else, so the base stays what its recorded hash stands for.
 // The rule of every item: each camera sample's radiance and the launch's sample, vertex and ray counts keep their bits (tests/test_lean_tiles_emu.py).
+// A re-timed item (TR_LEAN_FOLD_MIS_RAY) keeps them too and moves only the step a sample finishes in, i.e. the order of the film's f32 sums
+// (tests/test_lean_fold_emu.py, tests/test_gpu_lean_fold.py). It is not compiled into this library, whose code objects stay what their recorded hash
+// stands for: the instantiations it applies to -- LFILT = false -- are compiled with it into libtrayhip_foldmis.so (kernel_fold.h), and path_tiles /
+// path_tiles_kernel hand the launches without mis_ray_filter on to that library.
 #pragma once
 
 namespace tr_tiles {

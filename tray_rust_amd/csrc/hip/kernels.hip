@@ -380,25 +380,65 @@ __global__ __launch_bounds__(TR_BLOCK, (FEAT == 15 || INTEG != TRAY_INTEGRATOR_P
 #else
 #define TR_CLK(slot) ((void)0)
 #endif
+#ifdef TR_LEAN_FOLD_MIS_RAY
+            // FOLD (dev_integrator.h; the instantiations of PDF_FIRST): a wave with fewer than TR_LEAN_FOLD_MIN_LANES stage C rays does not enter the
+            // traversal for them. Its lanes without LF_MIS close the vertex where they always did; the ones with it keep the vertex open (LF_FOLD)
+            // and trace stage_c_ray in the next step's stage 0, beside the continuation rays -- both are closest-hit rays from bsdf.p over
+            // [0.001, inf) --, close the vertex there (vertex_end: the same operands in the same order, none of them written in between) and sit out
+            // the rest of that step: the continuation ray the PATH query prepared (ln.d, throughput) is traced a step later. Per sample nothing but
+            // the step it finishes in moves; samples, vertices and rays are counted as before.
+            constexpr bool FOLD = !LFILT && !ANIM && INTEG == TRAY_INTEGRATOR_PATH;
+            if (FOLD) ln.flags &= ~LF_SIT;
+#endif
 #pragma nounroll
             for (int stage = 0; stage < 3; ++stage) {
+#ifdef TR_LEAN_FOLD_MIS_RAY   // (LF_SIT: the lane closed a folded vertex in this step's stage 0 -- no shadow ray, no queries, no second vertex_end)
+                const bool alive = FOLD ? (ln.flags & (LF_ALIVE | LF_SIT)) == LF_ALIVE : (ln.flags & LF_ALIVE) != 0u;
+#else
                 const bool alive = (ln.flags & LF_ALIVE) != 0u;
+#endif
                 if (LFILT && stage == 2 && alive) mis_ray_filter<ANIM>(sc, ln);   // BSDF-sampled light rays that cannot hit the light are counted, not traced
                 const bool want_ray = alive && (stage == 0 || (stage == 1 && (ln.flags & LF_SHADOW)) || (stage == 2 && (ln.flags & LF_MIS)));
                 TraceResult tr_;
                 tr_.hit = false;
                 tr_.rec.t = 0.0f; tr_.rec.inst = 0xffffffffu; tr_.rec.prim = 0u; tr_.rec.b1 = 0.0f; tr_.rec.b2 = 0.0f;
+#ifdef TR_LEAN_FOLD_MIS_RAY
+                unsigned long long wr_ = __ballot(want_ray);
+                if (FOLD && stage == 2 && wr_ != 0ull && (uint32_t)__popcll(wr_) < (uint32_t)(TR_LEAN_FOLD_MIN_LANES)) {
+                    // too few stage C rays for a pass of their own (the vote is the base's: no new one): they wait for the next step's stage 0, which counts them
+                    if (want_ray) {
+                        ln.flags |= LF_FOLD;
+#ifdef TR_HOST_EMU   // tests/test_lean_fold_emu.py: how many rays were folded (tests/emu/emu_lean_tiles_fold.cpp)
+                        { extern unsigned long long tr_fold_rays; ++tr_fold_rays; }
+#endif
+                    }
+                    wr_ = 0ull;
+                }
+                const bool folded = FOLD && (ln.flags & LF_FOLD) != 0u;   // stage 0: the lane brought its open vertex's ray along; stage 2: the lane keeps its vertex open
+#else
                 const unsigned long long wr_ = __ballot(want_ray);
+#endif
                 w_rays += (uint32_t)__popcll(wr_);
                 if (LFILT && stage == 2) w_rays += (uint32_t)__popcll(__ballot(alive && (ln.flags & LF_MIS_MISS) != 0u));   // rays proven to miss the light (query_stage): counted like the reference's
                 if (wr_ != 0ull) {
+#ifdef TR_LEAN_FOLD_MIS_RAY   // (a folded lane's bounce is still its open vertex's, 0 at a camera ray's hit: stage_c_ray's min_t is 0.001 whatever it is)
+                    const Ray r = stage == 0 && !folded ? stage_a_ray(ln) : (stage == 1 ? stage_b_ray(ln) : stage_c_ray(ln));
+#else
                     const Ray r = stage == 0 ? stage_a_ray(ln) : (stage == 1 ? stage_b_ray(ln) : stage_c_ray(ln));
+#endif
                     tr_ = trace<ANIM, LFILT>(scp, my_stack, r, stage == 1, want_ray);
                 }
                 TR_CLK(stage);   // trace A / B / C
+#ifdef TR_LEAN_FOLD_MIS_RAY   // (a folded ray's hit is no new vertex)
+                if (stage == 0) w_vertices += (uint32_t)__popcll(__ballot(alive && !folded && tr_.hit));
+#ifdef TR_SAMPLE_DUMP
+                if (stage == 0 && alive && !folded && tr_.hit) ++dump_v;
+#endif
+#else
                 if (stage == 0) w_vertices += (uint32_t)__popcll(__ballot(alive && tr_.hit));
 #ifdef TR_SAMPLE_DUMP
                 if (stage == 0 && alive && tr_.hit) ++dump_v;
+#endif
 #endif
                 if (stage == 1) {
 #ifdef TR_LEAN_MIS_PDF_FIRST   // (not under LFILT -- a sphere light, whose pdf is never zero, or specular lobes --: smallpt gains nothing from the order and was slower with it, profiles/r19_lean_tiles.txt)
@@ -406,6 +446,18 @@ __global__ __launch_bounds__(TR_BLOCK, (FEAT == 15 || INTEG != TRAY_INTEGRATOR_P
 #else
                     vertex_queries<ANIM, FEAT>(sc, ln, tr_.hit, alive);   // (the whole wave enters: wave-aligned query passes)
 #endif
+#ifdef TR_LEAN_FOLD_MIS_RAY
+                } else if (alive) {
+                    // the vertex closes here in stage 2, unless the wave folds and the lane has a ray -- and in stage 0 for the lane that brought one along
+                    if (stage == 0 && !folded) {
+                        if (tr_.hit) vertex_begin<ANIM>(sc, ln, tr_.rec, cnt);
+                        else ln.flags &= ~LF_ALIVE;   // camera miss: black sample; continuation miss: path ends (path.rs:112-115)
+                    } else if (stage == 0 || !folded) {
+                        if (!vertex_end<ANIM>(sc, ln, tr_.hit, tr_.rec)) ln.flags &= ~LF_ALIVE;   // (a finished sample is splatted at the next step's start)
+                        if (stage == 0) ln.flags = (ln.flags & ~(LF_FOLD | LF_MIS)) | LF_SIT;
+                    }
+                }
+#else
                 } else if (alive) {
                     if (stage == 0) {
                         if (tr_.hit) vertex_begin<ANIM>(sc, ln, tr_.rec, cnt);
@@ -414,6 +466,7 @@ __global__ __launch_bounds__(TR_BLOCK, (FEAT == 15 || INTEG != TRAY_INTEGRATOR_P
                         if (!vertex_end<ANIM>(sc, ln, tr_.hit, tr_.rec)) ln.flags &= ~LF_ALIVE;
                     }
                 }
+#endif
                 TR_CLK(3 + stage);   // vertex_begin / queries / vertex_end
             }
         }

@@ -15,8 +15,9 @@ from _guided_ref import launches
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 DRIVER = r'''
-import ctypes as C, os, sys, types
+import ctypes as C, os, sys
 sys.path.insert(0, %(root)r)
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import numpy as np
 import tray_rust_amd as T
 from tray_rust_amd import _lib as L, scenes
@@ -67,30 +68,8 @@ elif mode == "launches":
     C.CDLL(None).hipDeviceSynchronize()   # (a wait the log must show: the check below has teeth)
 else:
     # Hip.denoise and Hip.render_denoised allocate through torch: a stand-in with host memory behind it, as the stand-in runtime's hipMalloc
-    class Tensor:
-        def __init__(self, a):
-            self.a = a; self.shape = a.shape; self.device = "cuda:0"
-        def data_ptr(self): return self.a.ctypes.data
-        def dim(self): return self.a.ndim
-        def to(self, *a): return self
-        def contiguous(self): return self
-        def reshape(self, *s): return Tensor(self.a.reshape(*s))
-        def cpu(self): return self
-        def numpy(self): return self.a
-    class Stream:
-        cuda_stream = 0x5150
-        def synchronize(self): pass
-    class Ctx:
-        def __enter__(self): return self
-        def __exit__(self, *a): return False
-    torch = types.ModuleType("torch")
-    torch.float32, torch.uint8 = np.float32, np.uint8
-    torch.from_numpy = lambda a: Tensor(a)
-    torch.empty = torch.zeros = lambda shape, dtype=None, device=None: Tensor(np.zeros(shape, dtype))
-    torch.empty_like = torch.zeros_like = lambda t: Tensor(np.zeros_like(t.a))
-    torch.device = lambda d: d
-    torch.cuda = types.SimpleNamespace(device=lambda d: Ctx(), current_stream=lambda: Stream())
-    sys.modules["torch"] = torch
+    from _fake_torch import Tensor, install as fake_torch
+    fake_torch()
     d = %(tmp)r
     scenes.write_assets(d, cornell=(64, 48, 16))
     scene, rt, spp, fi = T.Scene.load_file(os.path.join(d, "cornell_box.json"))

@@ -18,8 +18,9 @@ from _td2pass_ref import launches
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 DRIVER = r'''
-import ctypes as C, os, sys, types
+import ctypes as C, os, sys
 sys.path.insert(0, %(root)r)
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import numpy as np
 import tray_rust_amd as T
 from tray_rust_amd import _lib as L, scenes
@@ -55,36 +56,7 @@ def two_pass(w=W, h=H, e=even, o=odd, al=alb, n=1, nbs=None, ne=ZERO, no=ZERO, n
     ne, no, nal = arrays(nb[:n] if nbs is None else nbs, (ne, no, nal))
     return lib.tray_denoise_temporal_demodulated_two_pass_device(w, h, e, o, al, n, ne, no, nal, r, rt, f, k, r2, rt2, f2, k2, out_, s, stream)
 # Hip's entry points allocate through torch: a stand-in with host memory behind it, as the stand-in runtime's hipMalloc
-class Tensor:
-    count = 0
-    def __init__(self, a):
-        self.a = a; self.shape = a.shape; self.device = "cuda:0"
-    def data_ptr(self): return self.a.ctypes.data
-    def dim(self): return self.a.ndim
-    def to(self, *a): return self
-    def contiguous(self): return self
-    def clone(self): return Tensor(self.a.copy())
-    def zero_(self): self.a[...] = 0; return self
-    def cpu(self): return self
-    def numpy(self): return self.a
-class Stream:
-    cuda_stream = 0x5150
-    def synchronize(self): pass
-class Ctx:
-    def __enter__(self): return self
-    def __exit__(self, *a): return False
-def fake_torch():
-    torch = types.ModuleType("torch")
-    torch.float32, torch.uint8 = np.float32, np.uint8
-    torch.from_numpy = lambda a: Tensor(a)
-    def empty(shape, dtype=None, device=None):
-        Tensor.count += dtype is np.float32   # (the films; the scratch buffers are bytes, the outputs come from empty_like)
-        return Tensor(np.zeros(shape, dtype))
-    torch.empty = empty
-    torch.empty_like = lambda t: Tensor(np.zeros_like(t.a))
-    torch.device = lambda d: d
-    torch.cuda = types.SimpleNamespace(device=lambda d: Ctx(), current_stream=lambda: Stream())
-    sys.modules["torch"] = torch
+from _fake_torch import Tensor, install as fake_torch
 def with_film(j, i, p):
     t = list(nb[j]); t[i] = p; return tuple(t)
 if mode == "errors":

@@ -17,8 +17,9 @@ from _tdemod_ref import launches
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 DRIVER = r'''
-import ctypes as C, os, sys, types
+import ctypes as C, os, sys
 sys.path.insert(0, %(root)r)
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import numpy as np
 import tray_rust_amd as T
 from tray_rust_amd import _lib as L, scenes
@@ -47,36 +48,7 @@ def call(w=W, h=H, e=even, o=odd, a=alb, n=1, nbs=None, ne=0, no=0, na=0, r=7, r
     na = arr([p[2] for p in nbs]) if na == 0 else na
     return lib.tray_denoise_temporal_demodulated_device(w, h, e, o, a, n, ne, no, na, r, rt, f, k, out_, s, stream)
 # Hip's entry points allocate through torch: a stand-in with host memory behind it, as the stand-in runtime's hipMalloc
-class Tensor:
-    count = 0
-    def __init__(self, a):
-        self.a = a; self.shape = a.shape; self.device = "cuda:0"
-    def data_ptr(self): return self.a.ctypes.data
-    def dim(self): return self.a.ndim
-    def to(self, *a): return self
-    def contiguous(self): return self
-    def clone(self): return Tensor(self.a.copy())
-    def zero_(self): self.a[...] = 0; return self
-    def cpu(self): return self
-    def numpy(self): return self.a
-class Stream:
-    cuda_stream = 0x5150
-    def synchronize(self): pass
-class Ctx:
-    def __enter__(self): return self
-    def __exit__(self, *a): return False
-def fake_torch():
-    torch = types.ModuleType("torch")
-    torch.float32, torch.uint8 = np.float32, np.uint8
-    torch.from_numpy = lambda a: Tensor(a)
-    def empty(shape, dtype=None, device=None):
-        Tensor.count += dtype is np.float32   # (the films; the scratch buffers are bytes, the outputs come from empty_like)
-        return Tensor(np.zeros(shape, dtype))
-    torch.empty = empty
-    torch.empty_like = lambda t: Tensor(np.zeros_like(t.a))
-    torch.device = lambda d: d
-    torch.cuda = types.SimpleNamespace(device=lambda d: Ctx(), current_stream=lambda: Stream())
-    sys.modules["torch"] = torch
+from _fake_torch import Tensor, install as fake_torch
 if mode == "errors":
     T.check(lib.tray_init(0))
     nan = float("nan")

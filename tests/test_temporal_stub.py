@@ -12,8 +12,9 @@ from _temporal_ref import launches
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 DRIVER = r'''
-import ctypes as C, os, sys, types
+import ctypes as C, os, sys
 sys.path.insert(0, %(root)r)
+sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import numpy as np
 import tray_rust_amd as T
 from tray_rust_amd import _lib as L, scenes
@@ -60,29 +61,8 @@ elif mode == "launches":
     print("RC_DN", lib.tray_denoise_device(W, H, even, odd, 7, 3, 0.45, out, scratch, stream))
 else:
     # Hip.render_sequence_denoised allocates its films through torch: a stand-in with host memory behind it, as the stand-in runtime's hipMalloc
-    class Tensor:
-        count = 0
-        def __init__(self, shape, dtype):
-            self.a = np.zeros(shape, dtype); self.shape = self.a.shape; self.device = "cuda:0"
-        def data_ptr(self): return self.a.ctypes.data
-        def zero_(self): self.a[...] = 0; return self
-        def cpu(self): return self
-        def numpy(self): return self.a
-    class Stream:
-        cuda_stream = 0x5150
-        def synchronize(self): pass
-    class Ctx:
-        def __enter__(self): return self
-        def __exit__(self, *a): return False
-    torch = types.ModuleType("torch")
-    torch.float32, torch.uint8 = np.float32, np.uint8
-    def empty(shape, dtype=None, device=None):
-        Tensor.count += dtype is np.float32   # (the half films; the scratch buffers are bytes, the outputs come from empty_like)
-        return Tensor(shape, dtype)
-    torch.empty = empty
-    torch.empty_like = lambda t: Tensor(t.shape, t.a.dtype)
-    torch.cuda = types.SimpleNamespace(device=lambda d: Ctx(), current_stream=lambda: Stream())
-    sys.modules["torch"] = torch
+    from _fake_torch import Tensor, install as fake_torch
+    fake_torch()
     d = %(tmp)r
     os.makedirs(os.path.join(d, "models"), exist_ok=True)
     open(os.path.join(d, "models", "cube.obj"), "w").write(scenes.cube_obj())
@@ -91,7 +71,7 @@ else:
     scene, rt, spp, fi = T.Scene.load_file(scenes.write_scene(s, os.path.join(d, "four_frames.json")))
     hip = T.Hip(0, seed=3)
     cfg = T.Config(d, "four_frames.json", spp, 1, fi, (0, 0))
-    hip.render_samples_device(scene, 0, (0, 0), 16, (0, 8), Tensor((48, 64, 4), np.float32).data_ptr(), 0x5150)   # what one range launch looks like
+    hip.render_samples_device(scene, 0, (0, 0), 16, (0, 8), Tensor(np.zeros((48, 64, 4), np.float32)).data_ptr(), 0x5150)   # what one range launch looks like
     Tensor.count = 0
     for frame, img in hip.render_sequence_denoised(scene, cfg, range(4), reach=1):
         print("FRAME", frame, img.shape, img.dtype)

@@ -207,6 +207,36 @@ class Scene:
             pass
 
 
+# the nouns of the film intake's refusals (Hip._films_on_device): of the calls that take lists of frames, and of those that take one frame's films
+_FRAMES = {"frames": "frames", "albedo": "albedo films", "guides": "guides", "film": "a film must be (h, w, 4)", "albedo_kind_first": True}
+_FILMS = {"frames": "films", "albedo": "albedo film", "guides": "guide", "film": "even and odd must be two (h, w, 4) films of one size",
+          "albedo_kind_first": False}   # (albedo_kind_first: an albedo film of the wrong kind is refused before it is looked at, or after)
+
+
+def _ptr(tensor):
+    return C.c_void_p(tensor.data_ptr())
+
+
+def _current_stream():
+    """torch's current stream as the C calls take it"""
+    import torch
+    stream = torch.cuda.current_stream().cuda_stream
+    return C.c_void_p(stream) if stream else None
+
+
+def _scratch(nbytes, device):
+    """a call's scratch buffer (never empty); the caller synchronises before it lets go of it"""
+    import torch
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def _as_given(as_numpy, out):
+    """a tensor, or a tuple of them, as the kind the caller handed in"""
+    if isinstance(out, tuple):
+        return tuple(_as_given(as_numpy, t) for t in out)
+    return out.cpu().numpy() if as_numpy else out
+
+
 _PARTITIONS = {"tiles": _lib.TRAY_PARTITION_TILES, "samples": _lib.TRAY_PARTITION_SAMPLES}   # tray_multi_set_partition
 
 
@@ -238,9 +268,8 @@ class Hip:
         spp = self._select_sampler(dev, config.spp)
         start, count = config.select_blocks
         check(lib().tray_render_tiles(dev, int(start), int(count), spp, self.seed, rt.pixels.ctypes.data))
-        t = _lib.TrayKernelTiming()
-        if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
-            self.last_timing = t
+        t = self._keep_timing(dev)
+        if t is not None:
             print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
 
     def render_device(self, scene, frame, select_blocks, spp, rgbw_ptr, stream=None):
@@ -307,44 +336,43 @@ class Hip:
                 film.zero_()
                 self.render_samples_device(scene, config.current_frame, config.select_blocks, spp, (begin, end), film.data_ptr(), stream or None)
                 rt.add_pixels(film.cpu().numpy())
-                t = _lib.TrayKernelTiming()
-                if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
-                    self.last_timing = t
+                self._keep_timing(dev)
                 yield end, rt
+
+    def _keep_timing(self, dev):
+        """the timing of the device scene's last render call, kept as self.last_timing; None, and nothing kept, where the library has none"""
+        t = _lib.TrayKernelTiming()
+        if lib().tray_last_timing(dev, C.byref(t)) != _lib.TRAY_OK:
+            return None
+        self.last_timing = t
+        return t
 
     def _noise_target_device(self, dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out, max_ratio=None):
         """one noise-target call on the current stream into the zeroed (h, w, 4) tensors even / odd: error="raw" is
         tray_render_noise_target_device, "filtered" tray_render_noise_target_filtered_device (with its denoised output if want_out). max_ratio:
         tray_scene_set_noise_ratio for this call alone (the device scene is back at 0 afterwards). Returns (tile_samples, tile_error, out tensor
         or None)."""
-        if max_ratio is None:
-            return self._noise_target_call(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out)
-        check(lib().tray_scene_set_noise_ratio(dev, int(max_ratio)))
-        try:
-            return self._noise_target_call(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out)
-        finally:
-            lib().tray_scene_set_noise_ratio(dev, 0)   # (a device scene other methods reuse keeps their behaviour)
-
-    def _noise_target_call(self, dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, want_out):
         import torch
-        samples, err = np.zeros(n, np.uint32), np.zeros(n, np.float32)
-        sp, ep = samples.ctypes.data_as(C.POINTER(C.c_uint32)), err.ctypes.data_as(C.POINTER(C.c_float))
-        stream = torch.cuda.current_stream().cuda_stream
-        stream = C.c_void_p(stream) if stream else None
-        out = None
-        if error == "raw":
-            check(lib().tray_render_noise_target_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
-                                                        C.c_void_p(odd.data_ptr()), sp, ep, stream))
-        else:
-            h, w = int(even.shape[0]), int(even.shape[1])
-            scratch = torch.empty(max(int(lib().tray_noise_target_filtered_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=even.device)
-            out = torch.empty_like(even) if want_out else None
-            check(lib().tray_render_noise_target_filtered_device(dev, start, count, int(min_spp), spp, float(threshold), self.seed, C.c_void_p(even.data_ptr()),
-                                                                 C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k),
-                                                                 C.c_void_p(out.data_ptr()) if want_out else None, C.c_void_p(scratch.data_ptr()), sp, ep,
-                                                                 stream))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return samples, err, out
+        if max_ratio is not None:
+            check(lib().tray_scene_set_noise_ratio(dev, int(max_ratio)))
+        try:
+            samples, err = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+            head = (dev, start, count, int(min_spp), spp, float(threshold), self.seed, _ptr(even), _ptr(odd))
+            tail = (samples.ctypes.data_as(C.POINTER(C.c_uint32)), err.ctypes.data_as(C.POINTER(C.c_float)), _current_stream())
+            out = None
+            if error == "raw":
+                check(lib().tray_render_noise_target_device(*head, *tail))
+            else:
+                h, w = int(even.shape[0]), int(even.shape[1])
+                scratch = _scratch(lib().tray_noise_target_filtered_scratch_bytes(w, h), even.device)
+                out = torch.empty_like(even) if want_out else None
+                check(lib().tray_render_noise_target_filtered_device(*head, int(radius), int(patch), float(k), _ptr(out) if want_out else None,
+                                                                     _ptr(scratch), *tail))
+                torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+            return samples, err, out
+        finally:
+            if max_ratio is not None:
+                lib().tray_scene_set_noise_ratio(dev, 0)   # (a device scene other methods reuse keeps their behaviour)
 
     def render_noise_target(self, scene, rt, config, threshold, min_spp=16, error="raw", radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
                             k=_lib.TRAY_DENOISE_K, max_ratio=None):
@@ -369,38 +397,38 @@ class Hip:
             odd = torch.zeros_like(even)
             samples, err, _ = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, False, max_ratio)
             rt.add_pixels((even + odd).reshape(-1).cpu().numpy())
-        t = _lib.TrayKernelTiming()
-        if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:
-            self.last_timing = t
+        t = self._keep_timing(dev)
+        if t is not None:
             print(f"Frame {config.current_frame}: rendering took {t.render_ms * 1e-3:.4f}s")
         return samples, err
+
+    def _filter_call(self, stem, film, middle, outs, scratch_stem=None, scratch_args=()):
+        """The one device call of every filter: tray_denoise_<stem>_device(w, h, *middle, *outs, scratch, stream) on the current stream (stem "":
+        tray_denoise_device), the scratch buffer sized by the call's own tray_denoise_<stem>_scratch_bytes(w, h, *scratch_args), or by
+        scratch_stem's. film: one (h, w, 4) float32 tensor of the call, for the size and the device; middle: the arguments between the size and
+        the outputs as the C call takes them; outs: the output tensors, or how many to make, like `film`. Returns the tuple of outputs."""
+        import torch
+        h, w = int(film.shape[0]), int(film.shape[1])
+        name = lambda stem_, last: "_".join(part for part in ("tray_denoise", stem_, last) if part)
+        with torch.cuda.device(self.device):
+            if isinstance(outs, int):
+                outs = tuple(torch.empty_like(film) for _ in range(outs))
+            nbytes = getattr(lib(), name(stem if scratch_stem is None else scratch_stem, "scratch_bytes"))(w, h, *scratch_args)
+            scratch, stream = _scratch(nbytes, film.device), _current_stream()
+            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
+            check(getattr(lib(), name(stem, "device"))(w, h, *middle, *[_ptr(t) for t in outs], _ptr(scratch), stream))
+            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        return outs
 
     def _denoise_device(self, even, odd, radius, patch, k, second=None, albedo=None):
         """tray_denoise_device of two (h, w, 4) float32 tensors of this device on the current stream, or, with second = (radius2, patch2, k2),
         tray_denoise_two_pass_device; with an albedo film (a third such tensor) tray_denoise_demodulated_device of either; returns the output
         tensor"""
-        import torch
-        h, w = int(even.shape[0]), int(even.shape[1])
+        r2, f2, k2 = (0, 0, 1.0) if second is None else second   # (radius2 == 0: one pass)
+        films, first, again = (_ptr(even), _ptr(odd)), (int(radius), int(patch), float(k)), (int(r2), int(f2), float(k2))
         if albedo is not None:
-            nbytes = lambda w_, h_: lib().tray_denoise_demodulated_scratch_bytes(w_, h_, 0 if second is None else int(second[0]))
-        else:
-            nbytes = lib().tray_denoise_scratch_bytes if second is None else lib().tray_denoise_two_pass_scratch_bytes
-        with torch.cuda.device(self.device):
-            out = torch.empty_like(even)
-            scratch = torch.empty(max(int(nbytes(w, h)), 16), dtype=torch.uint8, device=even.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            head = (w, h, C.c_void_p(even.data_ptr()), C.c_void_p(odd.data_ptr()), int(radius), int(patch), float(k))
-            tail = (C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None)
-            if albedo is not None:
-                r2, f2, k2 = (0, 0, 1.0) if second is None else second   # (radius2 == 0: one pass)
-                check(lib().tray_denoise_demodulated_device(*head[:4], C.c_void_p(albedo.data_ptr()), *head[4:], int(r2), int(f2), float(k2), *tail))
-            elif second is None:
-                check(lib().tray_denoise_device(*head, *tail))
-            else:
-                check(lib().tray_denoise_two_pass_device(*head, int(second[0]), int(second[1]), float(second[2]), *tail))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out
+            return self._filter_call("demodulated", even, (*films, _ptr(albedo), *first, *again), 1, scratch_args=again[:1])[0]
+        return self._filter_call("" if second is None else "two_pass", even, (*films, *first, *(() if second is None else again)), 1)[0]
 
     @staticmethod
     def _second_pass(what, passes, radius2, patch2, k2):
@@ -409,38 +437,73 @@ class Hip:
             raise ValueError(f"{what}: passes must be 1 or 2, not {passes!r}")
         return None if passes == 1 else (radius2, patch2, k2)
 
-    def _films_on_device(self, what, even, odd):
-        """(as_numpy, e, o): two (h, w, 4) films -- numpy arrays or torch tensors on this device -- as two contiguous float32 tensors"""
+    def _films_on_device(self, what, frames, centre=0, albedos=None, guides=None, words=_FRAMES):
+        """The intake of every filter call: `frames` is a list of (even, odd) pairs of (h, w, 4) films, `albedos` one film per frame, `guides` one
+        (guide_a, guide_b) pair per frame -- numpy arrays, uploaded once, or torch tensors of this device, taken as they are --, all of one kind and
+        one size. Returns (as_numpy, rows): per frame the tuple (even, odd[, albedo][, guide_a, guide_b]) of contiguous float32 tensors, frames[centre]
+        first. A pair whose two films share their storage gets a copy of its second. `what` and `words` (_FRAMES for lists of frames, _FILMS for one
+        frame's films) are the caller's name and nouns in the refusals."""
         import torch
-        as_numpy = isinstance(even, np.ndarray)
-        if as_numpy != isinstance(odd, np.ndarray):
-            raise TypeError(f"{what}: even and odd must both be numpy arrays or both be torch tensors")
         dev = f"cuda:{self.device}"
-        if as_numpy:
-            e, o = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev) for x in (even, odd))
-        else:
-            if even.device != torch.device(dev) or odd.device != torch.device(dev):
-                raise ValueError(f"{what}: the films must live on {dev}")
-            e, o = (x.to(torch.float32).contiguous() for x in (even, odd))
-            if o.data_ptr() == e.data_ptr():
-                o = o.clone()
-        if e.dim() != 3 or e.shape[2] != 4 or e.shape != o.shape:
-            raise ValueError(f"{what}: even and odd must be two (h, w, 4) films of one size")
-        return as_numpy, e, o
+        is_numpy = lambda x: isinstance(x, np.ndarray)
 
-    def _film_on_device(self, what, film):
-        """one (h, w, 4) film -- a numpy array or a torch tensor on this device -- as a contiguous float32 tensor: uploaded once, or as it is"""
-        import torch
-        dev = f"cuda:{self.device}"
-        if isinstance(film, np.ndarray):
-            t = torch.from_numpy(np.ascontiguousarray(film, dtype=np.float32)).to(dev)
-        else:
-            if film.device != torch.device(dev):
+        def on_device(x):
+            if is_numpy(x):
+                return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+            if x.device != torch.device(dev):
                 raise ValueError(f"{what}: the films must live on {dev}")
-            t = film.to(torch.float32).contiguous()
-        if t.dim() != 3 or t.shape[2] != 4:
-            raise ValueError(f"{what}: a film must be (h, w, 4)")
-        return t
+            return x.to(torch.float32).contiguous()
+
+        def pairs(listed):
+            out = []
+            for even, odd in listed:
+                if is_numpy(even) != is_numpy(odd):
+                    raise TypeError(f"{what}: even and odd must both be numpy arrays or both be torch tensors")
+                e, o = on_device(even), on_device(odd)
+                if o.data_ptr() == e.data_ptr():
+                    o = o.clone()
+                if e.dim() != 3 or e.shape[2] != 4 or e.shape != o.shape:
+                    raise ValueError(f"{what}: even and odd must be two (h, w, 4) films of one size")
+                out.append((e, o))
+            if len({is_numpy(even) for even, _ in listed}) != 1:
+                raise TypeError(f"{what}: the frames must all be numpy arrays or all be torch tensors")
+            if any(e.shape != out[0][0].shape for e, _ in out):
+                raise ValueError(f"{what}: the frames must be of one size")
+            return out
+
+        frames, c = list(frames), int(centre)
+        albedos, guides = (None if x is None else list(x) for x in (albedos, guides))
+        if guides is not None and len(guides) != len(frames):
+            raise ValueError(f"{what}: guides must hold one pair of films per frame")
+        if not 0 <= c < len(frames):
+            raise ValueError(f"{what}: centre must index frames")
+        rows = pairs(frames)
+        as_numpy, size = is_numpy(frames[0][0]), rows[0][0].shape
+        if albedos is not None:
+            if len(albedos) != len(frames):
+                raise ValueError(f"{what}: albedos must hold one albedo film per frame")
+            kinds = TypeError(f"{what}: the {words['frames']} and the {words['albedo']} must all be numpy arrays or all be torch tensors")
+            mixed = any(is_numpy(a) != as_numpy for a in albedos)
+            if mixed and words["albedo_kind_first"]:
+                raise kinds
+            alb = []
+            for a in albedos:
+                alb.append(on_device(a))
+                if alb[-1].dim() != 3 or alb[-1].shape[2] != 4:
+                    raise ValueError(f"{what}: {words['film']}")
+            if mixed:
+                raise kinds
+            if any(a.shape != size for a in alb):
+                raise ValueError(f"{what}: the {words['albedo']} must have the {words['frames']}' size")
+            rows = [row + (a,) for row, a in zip(rows, alb)]
+        if guides is not None:
+            gpairs = pairs(guides)
+            if is_numpy(guides[0][0]) != as_numpy:
+                raise TypeError(f"{what}: the {words['frames']} and the {words['guides']} must all be numpy arrays or all be torch tensors")
+            if gpairs[0][0].shape != size:
+                raise ValueError(f"{what}: the {words['guides']} must have the {words['frames']}' size")
+            rows = [row + g for row, g in zip(rows, gpairs)]
+        return as_numpy, [rows[c]] + rows[:c] + rows[c + 1:]
 
     def denoise(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, passes=1,
                 radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2, k2=_lib.TRAY_DENOISE_K2, albedo=None):
@@ -451,62 +514,30 @@ class Hip:
         averages the films again. albedo: a first-hit albedo film of the same frame (render_first_hit), of the films' kind and size: the
         colour is divided by it, the remainder filtered and the texture multiplied back in (tray_denoise_demodulated_device)."""
         second = self._second_pass("denoise", passes, radius2, patch2, k2)
-        as_numpy, e, o = self._films_on_device("denoise", even, odd)
-        alb = None
-        if albedo is not None:
-            albedo_numpy, alb, _ = self._films_on_device("denoise", albedo, albedo)
-            if albedo_numpy != as_numpy:
-                raise TypeError("denoise: the films and the albedo film must all be numpy arrays or all be torch tensors")
-            if alb.shape != e.shape:
-                raise ValueError("denoise: the albedo film must have the films' size")
-        out = self._denoise_device(e, o, radius, patch, k, second, *(() if alb is None else (alb,)))
-        return out.cpu().numpy() if as_numpy else out
+        as_numpy, ((e, o, *alb),) = self._films_on_device("denoise", [(even, odd)], albedos=None if albedo is None else [albedo], words=_FILMS)
+        return _as_given(as_numpy, self._denoise_device(e, o, radius, patch, k, second, *alb))
 
     def denoise_guided(self, even, odd, guide_a, guide_b, radius=_lib.TRAY_DENOISE_RADIUS2, patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
         """denoise() with the weights measured on another pair of films (tray_denoise_guided_device): the patch distances come from (guide_a,
         guide_b), e.g. denoise_halves() of the same films, the averaged colours from (even, odd). Films in and out as for denoise(), all four of
         one kind and one size. With the films as their own guide the image is denoise()'s to the bit."""
-        import torch
-        as_numpy, e, o = self._films_on_device("denoise_guided", even, odd)
-        guide_numpy, ga, gb = self._films_on_device("denoise_guided", guide_a, guide_b)
-        if guide_numpy != as_numpy:
-            raise TypeError("denoise_guided: the films and the guide must all be numpy arrays or all be torch tensors")
-        if ga.shape != e.shape:
-            raise ValueError("denoise_guided: the guide must have the films' size")
-        h, w = int(e.shape[0]), int(e.shape[1])
-        with torch.cuda.device(self.device):
-            out = torch.empty_like(e)
-            scratch = torch.empty(max(int(lib().tray_denoise_guided_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_guided_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), C.c_void_p(ga.data_ptr()),
-                                                   C.c_void_p(gb.data_ptr()), int(radius), int(patch), float(k), C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
-        return out.cpu().numpy() if as_numpy else out
+        as_numpy, (films,) = self._films_on_device("denoise_guided", [(even, odd)], guides=[(guide_a, guide_b)], words=_FILMS)
+        out, = self._filter_call("guided", films[0], (*[_ptr(t) for t in films], int(radius), int(patch), float(k)), 1)
+        return _as_given(as_numpy, out)
 
     def _denoise_halves_device(self, e, o, radius, patch, k, fa, fb):
         """tray_denoise_halves_device over every block of two tensors of this device on the current stream, into the tensors fa and fb"""
-        import torch
-        h, w = int(e.shape[0]), int(e.shape[1])
-        with torch.cuda.device(self.device):
-            scratch = torch.empty(max(int(lib().tray_denoise_scratch_bytes(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(lib().tray_denoise_halves_device(w, h, C.c_void_p(e.data_ptr()), C.c_void_p(o.data_ptr()), int(radius), int(patch), float(k), None, 0,
-                                                   C.c_void_p(fa.data_ptr()), C.c_void_p(fb.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                                                   C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        self._filter_call("halves", e, (_ptr(e), _ptr(o), int(radius), int(patch), float(k), None, 0), (fa, fb), scratch_stem="")
 
     def denoise_halves(self, even, odd, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
         """The two cross-filtered halves (A, B) of denoise()'s filter (tray_denoise_halves_device), films in and out as there: (A.rgb + B.rgb) / 2
         is denoise()'s image to the bit, a half's weight is 1 where it exists and 0 where no neighbour had weight, and |A - B| / 2 is a per-pixel
         confidence map of the denoised frame."""
         import torch
-        as_numpy, e, o = self._films_on_device("denoise_halves", even, odd)
+        as_numpy, ((e, o),) = self._films_on_device("denoise_halves", [(even, odd)], words=_FILMS)
         fa, fb = torch.empty_like(e), torch.empty_like(e)
         self._denoise_halves_device(e, o, radius, patch, k, fa, fb)
-        return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
+        return _as_given(as_numpy, (fa, fb))
 
     def render_denoised(self, scene, rt, config, threshold=None, min_spp=16, radius=_lib.TRAY_DENOISE_RADIUS, patch=_lib.TRAY_DENOISE_PATCH,
                         k=_lib.TRAY_DENOISE_K, error="raw", passes=1, radius2=_lib.TRAY_DENOISE_RADIUS2, patch2=_lib.TRAY_DENOISE_PATCH2,
@@ -553,9 +584,7 @@ class Hip:
                 n = len(BlockQueue((w, h), (8, 8), (start, count)).blocks)
                 samples, err, out = self._noise_target_device(dev, start, count, min_spp, spp, threshold, even, odd, n, error, radius, patch, k, True, max_ratio)
                 result = (samples, err)
-            t = _lib.TrayKernelTiming()
-            if lib().tray_last_timing(dev, C.byref(t)) == _lib.TRAY_OK:   # (the last render call's: the whole noise-target call, or the second range)
-                self.last_timing = t
+            self._keep_timing(dev)   # (the last render call's: the whole noise-target call, or the second range)
             if out is None:
                 albedo = None
                 if demodulate:
@@ -571,22 +600,11 @@ class Hip:
         tuples of (h, w, 4) float32 tensors of this device -- (even, odd), then the albedo and / or the (guide_a, guide_b) the call takes --;
         first and the optional second are (radius, radius_t, patch, k). Returns the output tensor, or with `halves` the pair (fa, fb), written
         into `into` if given."""
-        import torch
-        e = centre[0]
-        h, w = int(e.shape[0]), int(e.shape[1])
         n = len(neighbours)
         # host arrays of device pointers, one per film of a frame (never of length 0)
         arrays = [(C.c_void_p * max(n, 1))(*[fr[i].data_ptr() for fr in neighbours]) for i in range(len(centre))]
         params = [v for r, rt, f, k in ([first] if second is None else [first, second]) for v in (int(r), int(rt), int(f), float(k))]
-        pointers = lambda tensors: [C.c_void_p(t.data_ptr()) for t in tensors]
-        with torch.cuda.device(self.device):
-            outs = (torch.empty_like(e),) if not halves else tuple(into) if into is not None else (torch.empty_like(e), torch.empty_like(e))
-            scratch = torch.empty(max(int(getattr(lib(), f"tray_denoise_{stem}_scratch_bytes")(w, h)), 16), dtype=torch.uint8, device=e.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            check(lib().tray_init(self.device))   # (the filter runs on the library's current device)
-            check(getattr(lib(), f"tray_denoise_{stem}_device")(w, h, *pointers(centre), n, *arrays, *params, *pointers(outs),
-                                                                 C.c_void_p(scratch.data_ptr()), C.c_void_p(stream) if stream else None))
-            torch.cuda.current_stream().synchronize()   # (scratch goes out of scope here)
+        outs = self._filter_call(stem, centre[0], (*[_ptr(t) for t in centre], n, *arrays, *params), 1 if not halves else 2 if into is None else tuple(into))
         return outs if halves else outs[0]
 
     def _denoise_temporal_device(self, centre, neighbours, radius, radius_t, patch, k, albedos=None):
@@ -605,48 +623,28 @@ class Hip:
         """tray_denoise_temporal_demodulated_halves_device of (even, odd, albedo) triples; returns (fa, fb), written into `into` if given"""
         return self._temporal_call("temporal_demodulated_halves", centre, neighbours, (radius, radius_t, patch, k), halves=True, into=into)
 
-    def _triples_on_device(self, what, frames, albedos, centre):
-        """(as_numpy, (even, odd, albedo) triples with frames[centre] first): _frames_on_device with one albedo film per frame, of the frames' kind
-        and size"""
-        frames, albedos = list(frames), list(albedos)
-        as_numpy, pairs = self._frames_on_device(what, frames, centre)
-        if len(albedos) != len(frames):
-            raise ValueError(f"{what}: albedos must hold one albedo film per frame")
-        if any(isinstance(a, np.ndarray) != as_numpy for a in albedos):
-            raise TypeError(f"{what}: the frames and the albedo films must all be numpy arrays or all be torch tensors")
-        alb = [self._film_on_device(what, a) for a in albedos]
-        if any(a.shape != pairs[0][0].shape for a in alb):
-            raise ValueError(f"{what}: the albedo films must have the frames' size")
-        c = int(centre)
-        return as_numpy, [pair + (a,) for pair, a in zip(pairs, [alb[c]] + alb[:c] + alb[c + 1:])]
-
     def denoise_temporal_demodulated_halves(self, frames, albedos, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
                                             patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K):
         """denoise_temporal_halves() of the frames divided by their own albedo films (tray_denoise_temporal_demodulated_halves_device): frames and
         albedos in as for denoise_temporal_demodulated(), two films out. The halves are NOT multiplied by the centre's texture: they are the
         guides of denoise_temporal_demodulated_guided(). A one-element list gives a frame's own halves in that domain."""
-        as_numpy, triples = self._triples_on_device("denoise_temporal_demodulated_halves", frames, albedos, centre)
-        fa, fb = self._denoise_temporal_demodulated_halves_device(triples[0], triples[1:], radius, radius_t, patch, k)
-        return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
+        as_numpy, triples = self._films_on_device("denoise_temporal_demodulated_halves", frames, centre, albedos)
+        return _as_given(as_numpy, self._denoise_temporal_demodulated_halves_device(triples[0], triples[1:], radius, radius_t, patch, k))
 
     def denoise_temporal_demodulated_guided(self, frames, albedos, guides, centre, radius=_lib.TRAY_DENOISE_RADIUS2, radius_t=_lib.TRAY_DENOISE_RADIUS_T2,
                                             patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
         """denoise_temporal_guided() of the frames divided by their own albedo films, times frames[centre]'s texture
         (tray_denoise_temporal_demodulated_guided_device): `guides` holds one (guide_a, guide_b) pair per frame, already in the demodulated domain,
         e.g. denoise_temporal_demodulated_halves() of the centre and of every other frame alone. All films of one kind and size, all different."""
-        frames, guides = list(frames), list(guides)
-        what = "denoise_temporal_demodulated_guided"
-        if len(guides) != len(frames):
-            raise ValueError(f"{what}: guides must hold one pair of films per frame")
-        as_numpy, triples = self._triples_on_device(what, frames, albedos, centre)
-        guide_numpy, gpairs = self._frames_on_device(what, guides, centre)
-        if guide_numpy != as_numpy:
-            raise TypeError(f"{what}: the frames and the guides must all be numpy arrays or all be torch tensors")
-        if gpairs[0][0].shape != triples[0][0].shape:
-            raise ValueError(f"{what}: the guides must have the frames' size")
-        both = [fr + g for fr, g in zip(triples, gpairs)]
-        out = self._temporal_call("temporal_demodulated_guided", both[0], both[1:], (radius, radius_t, patch, k))
-        return out.cpu().numpy() if as_numpy else out
+        as_numpy, rows = self._films_on_device("denoise_temporal_demodulated_guided", frames, centre, albedos, guides)
+        return _as_given(as_numpy, self._temporal_call("temporal_demodulated_guided", rows[0], rows[1:], (radius, radius_t, patch, k)))
+
+    def _denoise_temporal(self, what, frames, centre, albedos, first, second):
+        """denoise_temporal and denoise_temporal_demodulated after their own refusals: the films taken in, and the one call that `albedos` (a list,
+        or None) and `second` ((radius2, radius_t2, patch2, k2), or None) select"""
+        as_numpy, rows = self._films_on_device(what, frames, centre, albedos)
+        stem = "temporal" + ("_demodulated" if albedos is not None else "") + ("_two_pass" if second is not None else "")
+        return _as_given(as_numpy, self._temporal_call(stem, rows[0], rows[1:], first, second))
 
     def denoise_temporal_demodulated(self, frames, albedos, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
                                      patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, passes=2, radius2=_lib.TRAY_DENOISE_RADIUS2,
@@ -657,35 +655,16 @@ class Hip:
         in (tray_denoise_temporal_demodulated_two_pass_device). passes=1 is denoise_temporal(albedos=...), to the bit
         (tray_denoise_temporal_demodulated_device). A one-element list gives denoise(albedo=..., passes=2)'s image to the bit."""
         second = self._second_pass("denoise_temporal_demodulated", passes, radius2, patch2, k2)
-        as_numpy, triples = self._triples_on_device("denoise_temporal_demodulated", frames, albedos, centre)
-        if second is None:
-            out = self._temporal_call("temporal_demodulated", triples[0], triples[1:], (radius, radius_t, patch, k))
-        else:
-            out = self._temporal_call("temporal_demodulated_two_pass", triples[0], triples[1:], (radius, radius_t, patch, k), (radius2, radius_t2, patch2, k2))
-        return out.cpu().numpy() if as_numpy else out
-
-    def _frames_on_device(self, what, frames, centre):
-        """(as_numpy, pairs with frames[centre] first): a list of (even, odd) pairs of one kind and size as tensors of this device"""
-        frames = list(frames)
-        if not 0 <= int(centre) < len(frames):
-            raise ValueError(f"{what}: centre must index frames")
-        on_device = [self._films_on_device(what, even, odd) for even, odd in frames]
-        if len({kind for kind, _, _ in on_device}) != 1:
-            raise TypeError(f"{what}: the frames must all be numpy arrays or all be torch tensors")
-        pairs = [(e, o) for _, e, o in on_device]
-        if any(e.shape != pairs[0][0].shape for e, _ in pairs):
-            raise ValueError(f"{what}: the frames must be of one size")
-        c = int(centre)
-        return on_device[0][0], [pairs[c]] + pairs[:c] + pairs[c + 1:]
+        return self._denoise_temporal("denoise_temporal_demodulated", frames, centre, list(albedos), (radius, radius_t, patch, k),
+                                      second and (radius2, radius_t2, patch2, k2))
 
     def denoise_temporal_halves(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
                                 k=_lib.TRAY_DENOISE_K):
         """The two cross-filtered halves (A, B) of denoise_temporal()'s filter (tray_denoise_temporal_halves_device), frames in as there and two
         films out as from denoise_halves(): (A.rgb + B.rgb) / 2 is denoise_temporal()'s image to the bit, and a one-element list gives
         denoise_halves()'s films to the bit."""
-        as_numpy, pairs = self._frames_on_device("denoise_temporal_halves", frames, centre)
-        fa, fb = self._denoise_temporal_halves_device(pairs[0], pairs[1:], radius, radius_t, patch, k)
-        return (fa.cpu().numpy(), fb.cpu().numpy()) if as_numpy else (fa, fb)
+        as_numpy, pairs = self._films_on_device("denoise_temporal_halves", frames, centre)
+        return _as_given(as_numpy, self._denoise_temporal_halves_device(pairs[0], pairs[1:], radius, radius_t, patch, k))
 
     def denoise_temporal_guided(self, frames, guides, centre, radius=_lib.TRAY_DENOISE_RADIUS2, radius_t=_lib.TRAY_DENOISE_RADIUS_T2,
                                 patch=_lib.TRAY_DENOISE_PATCH2, k=_lib.TRAY_DENOISE_K2):
@@ -693,18 +672,8 @@ class Hip:
         per frame, e.g. denoise_temporal_halves() of the centre and denoise_halves() of every other frame; the patch distances come from them, the
         averaged colours from `frames`. All films of one kind and size. With the frames as their own guides the image is denoise_temporal()'s to
         the bit; a one-element list gives denoise_guided()'s."""
-        frames, guides = list(frames), list(guides)
-        if len(guides) != len(frames):
-            raise ValueError("denoise_temporal_guided: guides must hold one pair of films per frame")
-        as_numpy, pairs = self._frames_on_device("denoise_temporal_guided", frames, centre)
-        guide_numpy, gpairs = self._frames_on_device("denoise_temporal_guided", guides, centre)
-        if guide_numpy != as_numpy:
-            raise TypeError("denoise_temporal_guided: the frames and the guides must all be numpy arrays or all be torch tensors")
-        if gpairs[0][0].shape != pairs[0][0].shape:
-            raise ValueError("denoise_temporal_guided: the guides must have the frames' size")
-        both = [fr + g for fr, g in zip(pairs, gpairs)]
-        out = self._temporal_call("temporal_guided", both[0], both[1:], (radius, radius_t, patch, k))
-        return out.cpu().numpy() if as_numpy else out
+        as_numpy, rows = self._films_on_device("denoise_temporal_guided", frames, centre, guides=guides)
+        return _as_given(as_numpy, self._temporal_call("temporal_guided", rows[0], rows[1:], (radius, radius_t, patch, k)))
 
     def denoise_temporal(self, frames, centre, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH,
                          k=_lib.TRAY_DENOISE_K, albedos=None, passes=1, radius2=_lib.TRAY_DENOISE_RADIUS2, radius_t2=_lib.TRAY_DENOISE_RADIUS_T2,
@@ -721,24 +690,67 @@ class Hip:
         second = self._second_pass("denoise_temporal", passes, radius2, patch2, k2)
         if second is not None and albedos is not None:
             raise ValueError("denoise_temporal: passes=2 filters the films as they are; use albedos=None with it")
-        frames = list(frames)
-        as_numpy, pairs = self._frames_on_device("denoise_temporal", frames, centre)
-        c = int(centre)
-        if second is not None:
-            out = self._temporal_call("temporal_two_pass", pairs[0], pairs[1:], (radius, radius_t, patch, k), (radius2, radius_t2, patch2, k2))
-        elif albedos is None:
-            out = self._denoise_temporal_device(pairs[0], pairs[1:], radius, radius_t, patch, k)
-        else:
-            albedos = list(albedos)
-            if len(albedos) != len(frames):
-                raise ValueError("denoise_temporal: albedos must hold one albedo film per frame")
-            if any(isinstance(a, np.ndarray) != as_numpy for a in albedos):
-                raise TypeError("denoise_temporal: the frames and the albedo films must all be numpy arrays or all be torch tensors")
-            alb = [self._film_on_device("denoise_temporal", a) for a in albedos]
-            if any(a.shape != pairs[0][0].shape for a in alb):
-                raise ValueError("denoise_temporal: the albedo films must have the frames' size")
-            out = self._denoise_temporal_device(pairs[0], pairs[1:], radius, radius_t, patch, k, [alb[c]] + alb[:c] + alb[c + 1:])
-        return out.cpu().numpy() if as_numpy else out
+        return self._denoise_temporal("denoise_temporal", frames, centre, albedos, (radius, radius_t, patch, k), second and (radius2, radius_t2, patch2, k2))
+
+    def _render_sequence(self, what, scene, config, frames, reach, first, second, albedo, feature_spp):
+        """The loop of both sequence generators, with its checks in `what`'s name. Every frame of `frames` is rendered once into films of its own: its
+        two half films; with `albedo` its first-hit albedo film, from the samples [0, feature_spp or spp); with a second pass two more for its own
+        first-pass halves, computed right after the renders. They are held while a later frame's window reaches them and rendered into again
+        afterwards. Every frame is then filtered with the other frames of its window in ascending order: by one call with first = (radius, radius_t,
+        patch, k), or, with second = (radius2, radius_t2, patch2, k2), by its halves over the window (into the one pilot pair) and the guided call.
+        Yields (frame, rgbw)."""
+        import torch
+        frames, reach = [int(f) for f in frames], int(reach)
+        if any(b != a + 1 for a, b in zip(frames, frames[1:])):
+            raise ValueError(f"{what}: frames must be consecutive frame numbers")
+        if not 0 <= 2 * reach <= _lib.TRAY_DENOISE_MAX_NEIGHBOURS:
+            raise ValueError(f"{what}: 0 <= reach <= {_lib.TRAY_DENOISE_MAX_NEIGHBOURS // 2}")
+        if not frames:
+            return
+        spp = self._select_sampler(scene.device_scene(frames[0], self.device), config.spp)
+        if spp < 2:
+            raise ValueError(f"{what}: two half films need spp >= 2")
+        n_feat = spp if feature_spp is None else int(feature_spp)
+        if albedo and not 1 <= n_feat <= spp:
+            raise ValueError(f"{what}: feature_spp must lie in [1, {spp}]")
+        film = scene.flatten(frames[0]).contents.film
+        w, h = int(film.width), int(film.height)
+        n = 3 if albedo else 2   # the films of a frame that a filter reads: (even, odd[, albedo]); its own halves (fa, fb) follow them
+        held, spare = {}, []   # frame -> its films on the device; the films of frames that are done, to be rendered into again
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            new_film = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
+            throw_away = (new_film(), new_film()) if albedo else None   # the normal and depth films nobody reads
+            pilot = (new_film(), new_film()) if second is not None else None   # the halves of the frame in hand over all its frames
+            for f in frames:
+                window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
+                for g in window:
+                    if g not in held:
+                        films = spare.pop() if spare else tuple(new_film() for _ in range(n if second is None else n + 2))
+                        for half, rng in zip(films, ((0, spp // 2), (spp // 2, spp))):
+                            half.zero_()
+                            self.render_samples_device(scene, g, config.select_blocks, spp, rng, half.data_ptr(), stream or None)
+                        if albedo:
+                            for t in (films[2],) + throw_away:
+                                t.zero_()
+                            self.render_first_hit_device(scene, g, config.select_blocks, spp, (0, n_feat), films[2].data_ptr(),
+                                                         throw_away[0].data_ptr(), throw_away[1].data_ptr(), stream or None)
+                        # the frame's own first-pass halves, once: the guide it brings to its neighbours' second passes
+                        if second is not None and albedo:
+                            self._denoise_temporal_demodulated_halves_device(films[:3], [], *first, films[3:])
+                        elif second is not None:
+                            self._denoise_halves_device(films[0], films[1], first[0], first[2], first[3], films[2], films[3])
+                        held[g] = films
+                mine, others = held[f], [held[g] for g in window if g != f]
+                if second is None:
+                    out = self._denoise_temporal_device(mine[:2], [fr[:2] for fr in others], *first, *(([fr[2] for fr in [mine] + others],) if albedo else ()))
+                else:
+                    halves = self._denoise_temporal_demodulated_halves_device if albedo else self._denoise_temporal_halves_device
+                    halves(mine[:n], [fr[:n] for fr in others], *first, pilot)
+                    out = self._temporal_call("temporal_demodulated_guided" if albedo else "temporal_guided", mine[:n] + pilot, others, second)
+                for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
+                    spare.append(held.pop(g))
+                yield f, out.cpu().numpy()
 
     def render_sequence_denoised(self, scene, config, frames, reach=1, radius=_lib.TRAY_DENOISE_RADIUS, radius_t=_lib.TRAY_DENOISE_RADIUS_T,
                                  patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K, demodulate=False, feature_spp=None, passes=1,
@@ -754,58 +766,11 @@ class Hip:
         to the bit: every frame's own first-pass halves (denoise_halves) are computed once, when it is rendered, and kept with its films (at most
         2 reach + 1 such pairs and one pair for the centre's halves over all frames); it does not combine with demodulate.
         LowDiscrepancy only (TrayError TRAY_E_UNSUPPORTED otherwise)."""
-        import torch
         second = self._second_pass("render_sequence_denoised", passes, radius2, patch2, k2)
         if second is not None and demodulate:
             raise ValueError("render_sequence_denoised: passes=2 filters the films as they are; use demodulate=False with it")
-        frames, reach = [int(f) for f in frames], int(reach)
-        if any(b != a + 1 for a, b in zip(frames, frames[1:])):
-            raise ValueError("render_sequence_denoised: frames must be consecutive frame numbers")
-        if not 0 <= 2 * reach <= _lib.TRAY_DENOISE_MAX_NEIGHBOURS:
-            raise ValueError(f"render_sequence_denoised: 0 <= reach <= {_lib.TRAY_DENOISE_MAX_NEIGHBOURS // 2}")
-        if not frames:
-            return
-        spp = self._select_sampler(scene.device_scene(frames[0], self.device), config.spp)
-        if spp < 2:
-            raise ValueError("render_sequence_denoised: two half films need spp >= 2")
-        n_feat = spp if feature_spp is None else int(feature_spp)
-        if demodulate and not 1 <= n_feat <= spp:
-            raise ValueError(f"render_sequence_denoised: feature_spp must lie in [1, {spp}]")
-        film = scene.flatten(frames[0]).contents.film
-        w, h = int(film.width), int(film.height)
-        n_films = 3 if demodulate else 4 if second is not None else 2
-        held, spare = {}, []   # frame -> its (even, odd[, albedo | fa, fb]) on the device; the films of frames that are done, to be rendered into again
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            new_film = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
-            throw_away = (new_film(), new_film()) if demodulate else None   # the normal and depth films nobody reads
-            pilot = (new_film(), new_film()) if second is not None else None   # the halves of the frame in hand over all its frames
-            for f in frames:
-                window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
-                for g in window:
-                    if g not in held:
-                        films = spare.pop() if spare else tuple(new_film() for _ in range(n_films))
-                        for half, rng in zip(films, ((0, spp // 2), (spp // 2, spp))):
-                            half.zero_()
-                            self.render_samples_device(scene, g, config.select_blocks, spp, rng, half.data_ptr(), stream or None)
-                        if demodulate:
-                            for t in (films[2],) + throw_away:
-                                t.zero_()
-                            self.render_first_hit_device(scene, g, config.select_blocks, spp, (0, n_feat), films[2].data_ptr(),
-                                                         throw_away[0].data_ptr(), throw_away[1].data_ptr(), stream or None)
-                        if second is not None:   # the frame's own first-pass halves, once: the guide it brings to its neighbours' second passes
-                            self._denoise_halves_device(films[0], films[1], radius, patch, k, films[2], films[3])
-                        held[g] = films
-                others = [g for g in window if g != f]
-                if second is not None:
-                    self._denoise_temporal_halves_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k, pilot)
-                    out = self._temporal_call("temporal_guided", held[f][:2] + pilot, [held[g] for g in others], (radius2, radius_t2, patch2, k2))
-                else:
-                    out = self._denoise_temporal_device(held[f][:2], [held[g][:2] for g in others], radius, radius_t, patch, k,
-                                                        *(([held[g][2] for g in [f] + others],) if demodulate else ()))
-                for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
-                    spare.append(held.pop(g))
-                yield f, out.cpu().numpy()
+        yield from self._render_sequence("render_sequence_denoised", scene, config, frames, reach, (radius, radius_t, patch, k),
+                                         second and (radius2, radius_t2, patch2, k2), demodulate, feature_spp)
 
     def render_sequence_demodulated(self, scene, config, frames, reach=1, passes=2, feature_spp=None, radius=_lib.TRAY_DENOISE_RADIUS,
                                     radius_t=_lib.TRAY_DENOISE_RADIUS_T, patch=_lib.TRAY_DENOISE_PATCH, k=_lib.TRAY_DENOISE_K,
@@ -820,53 +785,12 @@ class Hip:
         albedo film and its two halves, rendered into again when the frame is done --, one throw-away normal and depth film and one pair for the
         centre's halves over all frames: 10 reach + 9. passes=1 is render_sequence_denoised(demodulate=True). LowDiscrepancy only (TrayError
         TRAY_E_UNSUPPORTED otherwise)."""
-        import torch
         second = self._second_pass("render_sequence_demodulated", passes, radius2, patch2, k2)
         if second is None:
             yield from self.render_sequence_denoised(scene, config, frames, reach, radius, radius_t, patch, k, demodulate=True, feature_spp=feature_spp)
             return
-        frames, reach = [int(f) for f in frames], int(reach)
-        if any(b != a + 1 for a, b in zip(frames, frames[1:])):
-            raise ValueError("render_sequence_demodulated: frames must be consecutive frame numbers")
-        if not 0 <= 2 * reach <= _lib.TRAY_DENOISE_MAX_NEIGHBOURS:
-            raise ValueError(f"render_sequence_demodulated: 0 <= reach <= {_lib.TRAY_DENOISE_MAX_NEIGHBOURS // 2}")
-        if not frames:
-            return
-        spp = self._select_sampler(scene.device_scene(frames[0], self.device), config.spp)
-        if spp < 2:
-            raise ValueError("render_sequence_demodulated: two half films need spp >= 2")
-        n_feat = spp if feature_spp is None else int(feature_spp)
-        if not 1 <= n_feat <= spp:
-            raise ValueError(f"render_sequence_demodulated: feature_spp must lie in [1, {spp}]")
-        film = scene.flatten(frames[0]).contents.film
-        w, h = int(film.width), int(film.height)
-        held, spare = {}, []   # frame -> its (even, odd, albedo, fa, fb) on the device; the films of frames that are done, to be rendered into again
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            new_film = lambda: torch.empty((h, w, 4), dtype=torch.float32, device=f"cuda:{self.device}")
-            throw_away = (new_film(), new_film())   # the normal and depth films nobody reads
-            pilot = (new_film(), new_film())   # the halves of the frame in hand over all its frames
-            for f in frames:
-                window = range(max(frames[0], f - reach), min(frames[-1], f + reach) + 1)
-                for g in window:
-                    if g not in held:
-                        films = spare.pop() if spare else tuple(new_film() for _ in range(5))
-                        for half, rng in zip(films, ((0, spp // 2), (spp // 2, spp))):
-                            half.zero_()
-                            self.render_samples_device(scene, g, config.select_blocks, spp, rng, half.data_ptr(), stream or None)
-                        for t in (films[2],) + throw_away:
-                            t.zero_()
-                        self.render_first_hit_device(scene, g, config.select_blocks, spp, (0, n_feat), films[2].data_ptr(), throw_away[0].data_ptr(),
-                                                     throw_away[1].data_ptr(), stream or None)
-                        # the frame's own demodulated first-pass halves, once: the guide it brings to its neighbours' second passes
-                        self._denoise_temporal_demodulated_halves_device(films[:3], [], radius, radius_t, patch, k, films[3:])
-                        held[g] = films
-                others = [g for g in window if g != f]
-                self._denoise_temporal_demodulated_halves_device(held[f][:3], [held[g][:3] for g in others], radius, radius_t, patch, k, pilot)
-                out = self._temporal_call("temporal_demodulated_guided", held[f][:3] + pilot, [held[g] for g in others], (radius2, radius_t2, patch2, k2))
-                for g in [g for g in held if g <= f - reach]:   # (no later frame's window reaches back to them)
-                    spare.append(held.pop(g))
-                yield f, out.cpu().numpy()
+        yield from self._render_sequence("render_sequence_demodulated", scene, config, frames, reach, (radius, radius_t, patch, k),
+                                         (radius2, radius_t2, patch2, k2), True, feature_spp)
 
     def render_shard_device(self, scene, frame, shard, n_shards, spp, rgbw_ptr, chunk_tiles=16, stream=None):
         """One rank's share of a frame (round-robin chunks of the Morton queue); merge = sum over ranks."""
